@@ -14,8 +14,16 @@ parameter gradient (+ all-reduce + Adam).
                nets, 2 M points; one step = one Adam step of PLATE:475-506.
 --config nc3d  configs[4]: 3-D Navier-Cauchy half space, 10x128 net on (x, y, z, t), 4 M points per GPU (32 M on 8); a build-side
                extension, not in the reference.
-Fresh Xavier weights, seed 1111, synthetic points.  Prints ONE JSON line on rank 0.  At N = 1 the default (wave) line also carries the
-small reference configuration configs[0] (4x32 net, 50 k points) timed on the GPU and on the host's cores.
+Fresh Xavier weights, seed 1111, synthetic points: the same arguments give the same inputs in every run.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, ramps the clock and warms up, times exactly K steps in one block, and prints the headline figures (`value`,
+`ms_per_step`, ...).  --full adds everything else: the K-step block repeated until a second of timed work has run (the median block
+is reported), the launch events, shader clock and roofline of the dominant kernel, the rocprofv3 --pmc traffic passes, the other
+precision modes, and the CPU baselines; at N = 1 the default (wave) line then also carries the small reference configuration
+configs[0] (4x32 net, 50 k points) timed on the GPU and on the host's cores.
+--dump-outputs DIR writes what the timed steps computed as DIR/<name>.npy: the parameters and Adam moments after the last timed step
+(float32) and the loss terms train() returned for every timed step (float64, one row per step).  With --full these are taken after
+the first timed block, i.e. after the same steps as in a plain run.
 """
 from __future__ import annotations
 
@@ -235,7 +243,11 @@ def main():
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "bf16", "f16", "bf16x3"])
     ap.add_argument("--chunk-points", type=int, default=1 << 18, help="points held in the spill workspace per pass (two-kernel path)")
     ap.add_argument("--ramp-steps", type=int, default=None, help="untimed clock-ramp steps before the warm-up steps")
-    ap.add_argument("--min-timed-seconds", type=float, default=1.0, help="repeat the K-step timed block until this much timed work has run (0: one block)")
+    ap.add_argument("--full", action="store_true", help="measure everything beside the headline figures (see the module docstring); "
+                    "a plain run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed steps computed to DIR/<name>.npy")
+    ap.add_argument("--min-timed-seconds", type=float, default=None, help="repeat the K-step timed block until this much timed work has run "
+                    "(default: 1 with --full, 0 = one block without)")
     ap.add_argument("--always-reduce", action="store_true", help="run the step's gradient all-reduce (and the buffer handling around it) also in a "
                     "process group of ONE rank: what one of N GPUs does per step, collective included, measured on a single GPU")
     ap.add_argument("--rank-share", type=int, default=1, help="N > 1 (one GPU, wave config): run what ONE of N data-parallel ranks executes per step -- 1/N of the "
@@ -245,12 +257,12 @@ def main():
                     "library's one-shot all-reduce over IPC-mapped peer buffers with Adam in the same kernel (pinn_p2p_*; wave config)")
     ap.add_argument("--no-step-call", action="store_true", help="wave config: make the step's library calls one by one (collocation kernel, side-set kernel, two "
                     "reductions, Adam: the round-4 sequence) instead of pinn_wave2d_step -- the same bits; for A / B timing on one box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc passes that measure roofline.traffic (N = 1 only; ~30-40 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the rocprofv3 --pmc passes that measure roofline.traffic (N = 1 only; ~30-40 s)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)      # the process those passes profile: the workload, a few untimed steps, no line
-    ap.add_argument("--no-small-config", action="store_true")
+    ap.add_argument("--no-small-config", action="store_true", help="--full: skip the 4x32 / 50 k configuration")
     ap.add_argument("--extra-modes", default="bf16,f16x3_fp16state",
-                    help="comma list of other modes to time briefly (wave, rank 0 / N=1): precision modes, or f16x3_fp16state = f16x3 with PINN_FLAG_STATE_FP16")
+                    help="--full: comma list of other modes to time briefly (wave, rank 0 / N=1): precision modes, or f16x3_fp16state = f16x3 with PINN_FLAG_STATE_FP16")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -393,18 +405,52 @@ def main():
             d = float(tt.item())
         return d, res
 
-    # The driver's K may make one block a tenth of a second (20 steps of 5.6 ms): box-to-box and clock noise are then +-2 %.  The block is
-    # therefore REPEATED until at least one second of timed work has run (same count on every rank: derived from the first block's
-    # rank-maximum time); `ms_per_step` / `value` are the MEDIAN block's, the spread is reported.
+    def outputs(losses):
+        """what a caller of the timed path holds after its last step: the parameters and Adam moments train() updated, and the loss
+        terms it returned for every step (rows: steps)"""
+        theta = model.theta["uv"] if isinstance(model.theta, dict) else model.theta
+        return {"theta": theta.detach().cpu().numpy(), "adam_m": model.adam_m.detach().cpu().numpy(), "adam_v": model.adam_v.detach().cpu().numpy(),
+                "losses": np.asarray(losses, dtype=np.float64).T}
+
+    # The driver's K may make one block a tenth of a second (20 steps of 5.6 ms): box-to-box and clock noise are then +-2 %.  With --full the
+    # block is therefore REPEATED until at least one second of timed work has run (same count on every rank: derived from the first block's
+    # rank-maximum time); `ms_per_step` / `value` are the MEDIAN block's, the spread is reported.  A plain run times one block of K steps.
+    min_timed_seconds = args.min_timed_seconds if args.min_timed_seconds is not None else (1.0 if args.full else 0.0)
     dts = []
     d, losses = timed_block()
     dts.append(d)
-    n_blocks = int(min(64, max(1, -(-args.min_timed_seconds // d)))) if args.min_timed_seconds > 0 else 1
+    dumped = outputs(losses) if args.dump_outputs and rank == 0 else None      # (the first block: the steps of a plain run, whatever follows)
+    n_blocks = int(min(64, max(1, -(-min_timed_seconds // d)))) if min_timed_seconds > 0 else 1
     for _ in range(n_blocks - 1):
         d, losses = timed_block()
         dts.append(d)
     dt = float(np.median(dts))
     value = (pts_per_rank if share > 1 else n_global) * steps / dt
+    ms_step = 1e3 * dt / steps
+    final_loss = float(losses[-1][-1]) if isinstance(losses, (tuple, list)) and len(losses[-1]) else None
+
+    if dumped is not None:
+        assert sum(a.nbytes for a in dumped.values()) <= 64 << 20, "--dump-outputs: more than 64 MB"
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a)
+
+    out = {
+        "metric": f"collocation-points/sec through PDE-residual loss+grad, {label} MLP",
+        "value": value, "unit": "collocation-points/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+        "ms_per_step": ms_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": args.precision, "data": "synthetic",
+        "timed_blocks": {"count": len(dts), "steps_per_block": steps, "block_ms_min": 1e3 * min(dts), "block_ms_median": 1e3 * dt, "block_ms_max": 1e3 * max(dts),
+                         "note": "every block = `steps` steps between barrier + synchronize brackets (max over ranks); ms_per_step and value are the median block's"},
+        "config": {"workload": workload, "bench_config": cfg, "collocation_points_global": n_global, "precision_mode": args.precision,
+                   "parallelism": f"dp{world}", "always_reduce": bool(args.always_reduce), "final_loss": final_loss, "algorithmic_flop_per_point": flop_pt,
+                   "step_call": not args.no_step_call},
+        "whole_path": {"achieved_tflops": flop_pt * value / 1e12, "frac_of_mfma_peak": flop_pt * value / 1e12 / (MFMA_PEAK_TFLOPS * world)},
+        "rank_share": share if share > 1 else None,
+    }
+    if not args.full:
+        emit(out, rank, stdout_fd)
+        return
 
     # ---- launch time of the dominant kernel under the SAME conditions as the timed steps: one more block of `steps` steps with the
     # library's asynchronous event ring armed (HIP events around every fused launch on its own stream, in stream order, no
@@ -433,7 +479,6 @@ def main():
     eng.lib.set_stamp_buffer(None)
     collo_ms = ring_ms[ring_streams >= 4]
     side_ms = ring_ms[ring_streams == 1]
-    ms_step = 1e3 * dt / steps
 
     def launch_stat():
         """the dominant launch's duration for the roofline: MEDIAN of the bracketed launches; checked against the step it is a part of
@@ -466,18 +511,8 @@ def main():
         evs = model.collective_events
         allreduce_ms = float(np.mean([a.elapsed_time(b) for a, b in evs[len(evs) // 2:]]))      # (second half: warm)
         model.collective_events = None
-    final_loss = float(losses[-1][-1]) if isinstance(losses, (tuple, list)) and len(losses[-1]) else None
 
-    out = {
-        "metric": f"collocation-points/sec through PDE-residual loss+grad, {label} MLP",
-        "value": value, "unit": "collocation-points/s", "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": 1e3 * dt / steps, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": args.precision, "data": "synthetic",
-        "timed_blocks": {"count": len(dts), "steps_per_block": steps, "block_ms_min": 1e3 * min(dts), "block_ms_median": 1e3 * dt, "block_ms_max": 1e3 * max(dts),
-                         "note": "every block = `steps` steps between barrier + synchronize brackets (max over ranks); ms_per_step and value are the median block's"},
-        "config": {"workload": workload, "bench_config": cfg, "collocation_points_global": n_global, "precision_mode": args.precision,
-                   "parallelism": f"dp{world}", "always_reduce": bool(args.always_reduce), "final_loss": final_loss, "algorithmic_flop_per_point": flop_pt},
-        "whole_path": {"achieved_tflops": flop_pt * value / 1e12, "frac_of_mfma_peak": flop_pt * value / 1e12 / (MFMA_PEAK_TFLOPS * world)},
+    out.update({
         "shader_clock_ghz": shader_clock_ghz,
         "shader_clock_note": "shader cycles of workgroup 0 between its first and its last step of one launch / the device wall-clock time (constant rate, "
                              "hipDeviceAttributeWallClockRate) of the same interval, both stamped by the kernel (workgroup0_ms; no host event in it): the clock "
@@ -488,8 +523,7 @@ def main():
         "mcycles_per_step_note": "ms_per_step x shader_clock_ghz: million shader cycles per step -- the figure that compares across boxes (the kernel is power-limited "
                                  "and boxes differ by +-2.5 % in clock)",
         "allreduce_ms": allreduce_ms,
-        "rank_share": share if share > 1 else None,
-    }
+    })
     if allreduce_ms is not None:
         out["allreduce_note"] = ("mean of timing events recorded on the step's stream around torch.distributed.all_reduce of the fused buffer "
                                  f"[gradient | loss sums] ({4 * model._buf.numel()} bytes), backend {backend}, world {world}"
@@ -497,7 +531,6 @@ def main():
                                  f"mean of timing events recorded on the step's stream around the one-shot P2P all-reduce kernel (push to every peer's IPC-mapped "
                                  f"slot, sum in rank order, Adam update in the same kernel: pinn_p2p_allreduce), {4 * model._buf.numel()} bytes, world {world}")
         out["config"]["collective"] = args.collective
-    out["config"]["step_call"] = not args.no_step_call
     if rank == 0:
         ls = launch_stat()
         # MFMAs issued per algorithmic product (forward and reverse chain: 8 of 12 contractions, 3 per product; weight gradient: 4 of 12): the
@@ -653,6 +686,11 @@ def main():
                     out["cpu_baseline"] = cpu_baseline_plate(c)
                 else:
                     out["cpu_baseline"] = cpu_baseline([3] + 8 * [args.width] + [7], 32768, 3, f"8x{args.width}")
+    emit(out, rank, stdout_fd)
+
+
+def emit(out, rank, stdout_fd):
+    """leave the process group together, give the real stdout back, and print rank 0's line"""
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.barrier()          # rank 0 is still profiling its kernel: leave together
         torch.distributed.destroy_process_group()

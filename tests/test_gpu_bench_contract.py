@@ -25,7 +25,7 @@ def run_bench(args, env=None, launcher=None):
                                        ("plate", ["--points-per-gpu", "120000"]),
                                        ("nc3d", ["--points-per-gpu", "65536"])])
 def test_bench_line(cfg, extra):
-    d = run_bench(["--config", cfg, "--steps", "4", "--warmup", "1", "--ramp-steps", "2", "--no-cpu-baseline"] + ([] if cfg == "nc3d" else ["--no-traffic"]) + extra)
+    d = run_bench(["--config", cfg, "--full", "--steps", "4", "--warmup", "1", "--ramp-steps", "2", "--no-cpu-baseline"] + ([] if cfg == "nc3d" else ["--no-traffic"]) + extra)
     assert REQUIRED <= set(d), sorted(REQUIRED - set(d))
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["higher_is_better"] is True and d["vs_baseline"] is None
     assert d["unit"] == "collocation-points/s" and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f16x3" and d["data"] == "synthetic"
@@ -73,10 +73,10 @@ def test_bench_line(cfg, extra):
 
 
 def test_bench_line_of_the_drivers_exact_command_is_self_consistent():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- the command the driver records as BENCH_rNN.json.  Round 5's record contradicted itself
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the driver's command with everything measured.  Round 5's record contradicted itself
     (four bracketed launches, their mean above ms_per_step, rest_of_step negative, roofline.frac 0.1185 beside whole_path 0.1242).  Now: >= 32
     bracketed launches whatever --steps is, the MEDIAN launch is the roofline's, the line checks launch <= 1.01 x step + 0.04 itself."""
-    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    d = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
     r, ls = d["roofline"], d["roofline"]["launch_stat"]
     assert d["steps"] == 20 and d["warmup"] == 5 and d["config"]["collocation_points_global"] == 2_000_000
     assert r["launches_timed"] >= 32 and ls["launches_timed"] == r["launches_timed"] and ls["launch_events_inconsistent"] is False
@@ -96,6 +96,28 @@ def test_bench_line_of_the_drivers_exact_command_is_self_consistent():
         assert 5e3 < r["traffic"] / 2_000_000 < 11e3, td
 
 
+def test_plain_bench_times_exactly_its_steps_and_dumps_what_they_computed(tmp_path):
+    """a plain run times exactly --steps steps in one block and measures nothing beside the headline; --dump-outputs writes the parameters,
+    Adam moments and per-step loss terms of the timed steps.  The inputs are seeded, so a --full run of the same workload dumps the same
+    outputs (taken after its first block: the same steps)"""
+    import numpy as np
+    args = ["--steps", "5", "--warmup", "2", "--points-per-gpu", "131072"]
+    a = run_bench(args + ["--dump-outputs", str(tmp_path / "plain")])
+    assert REQUIRED - {"roofline"} <= set(a) and not {"roofline", "shader_clock_ghz", "cpu_baseline", "small_config", "other_precision_modes"} & set(a)
+    assert a["steps"] == 5 and a["warmup"] == 2 and a["timed_blocks"]["count"] == 1 and a["value"] > 0
+    assert abs(a["timed_blocks"]["block_ms_median"] / 5 - a["ms_per_step"]) < 1e-6
+    b = run_bench(args + ["--dump-outputs", str(tmp_path / "full"), "--full", "--no-traffic", "--no-cpu-baseline", "--extra-modes", "none", "--no-small-config"])
+    assert "roofline" in b and b["steps"] == 5
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == ["adam_m.npy", "adam_v.npy", "losses.npy", "theta.npy"] and sorted(os.listdir(tmp_path / "full")) == names
+    za, zb = ({n: np.load(os.path.join(tmp_path, k, n)) for n in names} for k in ("plain", "full"))
+    assert sum(z.nbytes for z in za.values()) <= 64 << 20 and all(z.dtype in (np.float32, np.float64) for z in za.values())
+    assert za["losses.npy"].shape == (5, 5) and za["theta.npy"].shape == za["adam_m.npy"].shape == za["adam_v.npy"].shape
+    for n in names:
+        assert np.all(np.isfinite(za[n])), n
+        assert np.linalg.norm(za[n] - zb[n]) <= 1e-5 * np.linalg.norm(za[n]), n
+
+
 def test_bench_two_ranks_strong_scaling_gloo():
     """the multi-process path on one GPU: 2 ranks, gloo, fixed total work split over the ranks"""
     d = run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--ramp-steps", "1", "--scaling", "strong", "--global-points", "200000", "--no-cpu-baseline",
@@ -108,7 +130,7 @@ def test_bench_two_ranks_strong_scaling_gloo():
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2 ...` WITHOUT a launcher -- the form the driver uses for N = 1 -- spawns its two ranks itself (on a one-GPU box
     the ranks share the device over gloo) and prints rank 0's single line with n_gpus = 2"""
-    d = run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--ramp-steps", "1", "--points-per-gpu", "100000", "--no-cpu-baseline",
+    d = run_bench(["--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--ramp-steps", "1", "--points-per-gpu", "100000", "--no-cpu-baseline",
                    "--extra-modes", "none", "--no-small-config"], env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["collocation_points_global"] == 200000 and d["value"] > 0
     assert d["config"]["parallelism"] == "dp2" and d["roofline"]["launches_timed"] >= 3
@@ -117,7 +139,7 @@ def test_bench_launches_its_own_ranks():
 def test_bench_always_reduce_runs_the_collective_branch_on_one_gpu():
     """--always-reduce: a process group of ONE rank under nccl (= RCCL); the step then holds the all-reduce and the buffer handling around
     it, i.e. what one of N GPUs does per step"""
-    base = ["--steps", "4", "--warmup", "1", "--ramp-steps", "2", "--points-per-gpu", "131072", "--no-cpu-baseline", "--extra-modes", "none", "--no-small-config"]
+    base = ["--full", "--steps", "4", "--warmup", "1", "--ramp-steps", "2", "--points-per-gpu", "131072", "--no-cpu-baseline", "--extra-modes", "none", "--no-small-config"]
     d = run_bench(base + ["--always-reduce"], env={"HSA_ENABLE_IPC_MODE_LEGACY": "0", "MASTER_PORT": "29671"})
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["parallelism"] == "dp1"
     assert "always_reduce" in d["config"] and d["config"]["always_reduce"] is True
@@ -126,7 +148,7 @@ def test_bench_always_reduce_runs_the_collective_branch_on_one_gpu():
 
 def test_bench_rank_share_runs_one_ranks_share_of_every_set():
     """--rank-share 8: 1/8 of the collocation rows AND of the side sets (round 4 fed the whole side sets to the "one of 8 GPUs" figure)"""
-    d = run_bench(["--steps", "4", "--warmup", "1", "--ramp-steps", "2", "--global-points", "400000", "--rank-share", "8", "--always-reduce", "--no-cpu-baseline",
+    d = run_bench(["--full", "--steps", "4", "--warmup", "1", "--ramp-steps", "2", "--global-points", "400000", "--rank-share", "8", "--always-reduce", "--no-cpu-baseline",
                    "--extra-modes", "none", "--no-small-config"], env={"HSA_ENABLE_IPC_MODE_LEGACY": "0", "MASTER_PORT": "29673"})
     assert d["rank_share"] == 8 and d["n_gpus"] == 1 and d["config"]["collocation_points_global"] == 400000
     assert "50000 collocation pts per GPU" in d["config"]["workload"] and "IC 1275 + SRC 8800" in d["config"]["workload"]

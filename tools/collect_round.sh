@@ -20,17 +20,17 @@ cp $OUT/pmc_prod_conf/summary.json $OUT/${TAG}_conf_pmc_summary.json
 # take the place of the committed ones on the box, and are copied into profiles/ from gpurun_out/ afterwards
 cp $OUT/${TAG}_*_pmc_summary.json profiles/
 fi
-python bench.py > $OUT/${TAG}_bench_wave.json 2> $OUT/bench_wave.err
-python bench.py --config plate > $OUT/${TAG}_bench_plate.json 2> $OUT/bench_plate.err
-python bench.py --config plate --width 70 --no-cpu-baseline > $OUT/${TAG}_bench_plate70.json 2> $OUT/bench_plate70.err
-python bench.py --config nc3d > $OUT/${TAG}_bench_nc3d.json 2> $OUT/bench_nc3d.err
-python bench.py --width 80 --points-per-gpu 1000000 --no-cpu-baseline --extra-modes none > $OUT/${TAG}_bench_wave80.json 2> $OUT/bench_wave80.err
-python bench.py --width 100 --points-per-gpu 1000000 --no-cpu-baseline --extra-modes none > $OUT/${TAG}_bench_wave100.json 2> $OUT/bench_wave100.err
+python bench.py --full > $OUT/${TAG}_bench_wave.json 2> $OUT/bench_wave.err
+python bench.py --full --config plate > $OUT/${TAG}_bench_plate.json 2> $OUT/bench_plate.err
+python bench.py --full --config plate --width 70 --no-cpu-baseline > $OUT/${TAG}_bench_plate70.json 2> $OUT/bench_plate70.err
+python bench.py --full --config nc3d > $OUT/${TAG}_bench_nc3d.json 2> $OUT/bench_nc3d.err
+python bench.py --full --width 80 --points-per-gpu 1000000 --no-cpu-baseline --extra-modes none > $OUT/${TAG}_bench_wave80.json 2> $OUT/bench_wave80.err
+python bench.py --full --width 100 --points-per-gpu 1000000 --no-cpu-baseline --extra-modes none > $OUT/${TAG}_bench_wave100.json 2> $OUT/bench_wave100.err
 python tools/conf_time.py > $OUT/${TAG}_conf_time.txt 2>&1
 # what ONE of 8 ranks of the 2 M-point strong-scaling run executes per step (1/8 of every set), without and with the collective branch (RCCL; P2P)
-python bench.py --global-points 2000000 --rank-share 8 --no-cpu-baseline --extra-modes none --no-small-config > $OUT/${TAG}_bench_250k.json 2> $OUT/bench_250k.err
-python bench.py --global-points 2000000 --rank-share 8 --always-reduce --no-cpu-baseline --extra-modes none --no-small-config > $OUT/${TAG}_bench_250k_rccl.json 2> $OUT/bench_250k_rccl.err
-python bench.py --global-points 2000000 --rank-share 8 --always-reduce --collective p2p --no-cpu-baseline --extra-modes none --no-small-config > $OUT/${TAG}_bench_250k_p2p.json 2> $OUT/bench_250k_p2p.err
+python bench.py --full --global-points 2000000 --rank-share 8 --no-cpu-baseline --extra-modes none --no-small-config > $OUT/${TAG}_bench_250k.json 2> $OUT/bench_250k.err
+python bench.py --full --global-points 2000000 --rank-share 8 --always-reduce --no-cpu-baseline --extra-modes none --no-small-config > $OUT/${TAG}_bench_250k_rccl.json 2> $OUT/bench_250k_rccl.err
+python bench.py --full --global-points 2000000 --rank-share 8 --always-reduce --collective p2p --no-cpu-baseline --extra-modes none --no-small-config > $OUT/${TAG}_bench_250k_p2p.json 2> $OUT/bench_250k_p2p.err
 python tools/phase_trace_3d.py > $OUT/${TAG}_nc3d_phase_trace.txt 2>&1
 for f in $OUT/${TAG}_bench_*.json; do python - "$f" <<'PY'
 import json, sys
