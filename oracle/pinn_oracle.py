@@ -279,6 +279,57 @@ def data_loss_grad(params, layers, x, y, t, lb, ub, normalize, targets=None, out
     return sumsq, pack_params(Wbar, bbar, dtype), d
 
 
+def _plane_wave_2d_streams(kind, X, k_dir, amp, wavelength, E, mu, rho, plane_strain, speed):
+    """Fields (u, v, ut, vt, s11, s22, s12) of a 2-D plane wave and their streams (value, d/dx, d/dy, d/dt, d2/dt2): [5][N,7]."""
+    c1, c2, G = hooke_coeffs(E, mu, plane_strain)
+    kd = np.asarray(k_dir, dtype=np.float64)
+    kd = kd / np.linalg.norm(kd)
+    if kind == "P":
+        d, c = kd, np.sqrt(c1 / rho)
+    else:
+        d, c = np.array([-kd[1], kd[0]]), np.sqrt(G / rho)
+    if speed is not None:
+        c = float(speed)
+    k = 2.0 * np.pi / wavelength
+    kv = k * kd
+    om = k * c
+    ph = X[:, :2] @ kv - om * X[:, 2]
+    s, co = np.sin(ph), np.cos(ph)
+    gp = (kv[0], kv[1], -om)
+    N = X.shape[0]
+    S = np.zeros((5, N, 7))
+    for i in range(2):
+        S[0][:, i] = amp * d[i] * s
+        S[0][:, 2 + i] = -amp * d[i] * om * co
+        for a in range(3):
+            S[1 + a][:, i] = amp * d[i] * co * gp[a]
+            S[1 + a][:, 2 + i] = amp * d[i] * om * s * gp[a]
+        S[4][:, i] = -amp * d[i] * om * om * s
+        S[4][:, 2 + i] = amp * d[i] * om ** 3 * co
+    e11, e22, e12 = amp * d[0] * kv[0], amp * d[1] * kv[1], amp * (d[0] * kv[1] + d[1] * kv[0])      # strain amplitudes (times cos(ph))
+    for col, sig in ((4, c1 * e11 + c2 * e22), (5, c2 * e11 + c1 * e22), (6, G * e12)):
+        S[0][:, col] = sig * co
+        for a in range(3):
+            S[1 + a][:, col] = -sig * s * gp[a]
+        S[4][:, col] = -sig * om * om * co
+    return S
+
+
+def plane_wave_2d(kind, X, k_dir, amp=0.1, wavelength=7.0, E=2.5, mu=0.25, rho=1.0, plane_strain=True, speed=None):
+    """Exact plane-wave solution of the 2-D elastodynamic head (wave2d_residuals) sampled at X [N,3] = (x, y, t): returns
+    (Y [N,7], dY [3][N,7]).  kind 'P': displacement along k, speed sqrt(c1/rho); 'S': displacement normal to k, speed sqrt(G/rho),
+    with (c1, c2, G) = hooke_coeffs(E, mu, plane_strain) (c1 = c2 + 2 G in both laws).  ``speed`` overrides the speed (a wrong wave)."""
+    S = _plane_wave_2d_streams(kind, np.asarray(X, dtype=np.float64), k_dir, amp, wavelength, E, mu, rho, plane_strain, speed)
+    return S[0], [S[1], S[2], S[3]]
+
+
+def plane_wave_plate(kind, X, k_dir, amp=0.1, wavelength=7.0, E=20.0, mu=0.25, rho=1.0, plane_strain=False, speed=None):
+    """The same wave as the plate's five-stream input of plate_oracle.plate_residuals: F [5 streams (value, x, y, t, tt)][5 fields
+    (u, v, s11, s22, s12)][N].  The plate head is plane stress; ``plane_strain=True`` builds a wave of the other law."""
+    S = _plane_wave_2d_streams(kind, np.asarray(X, dtype=np.float64), k_dir, amp, wavelength, E, mu, rho, plane_strain, speed)
+    return np.stack([S[k][:, [0, 1, 4, 5, 6]].T for k in range(5)])
+
+
 # ----------------------------------------------------------------------------
 # loss layouts of the three wave scripts
 # ----------------------------------------------------------------------------

@@ -732,19 +732,20 @@ def test_hole_traction_through_the_fused_one_stream_kernel_emulated(emu, lN, n):
     assert not np.array_equal(res[1][1], res[0][1])          # two different code paths ran
 
 
-def _step_case(emu, layers, n, n_side, prec, seed, with_adam):
+def _step_case(emu, layers, n, n_side, prec, seed, with_adam, consts=(2.5, 0.25, 1.0), lb=LB, ub=UB):
     """pinn_wave2d_step against pinn_wave2d_loss_grad + pinn_data_loss_grad_multi (+ pinn_adam_step) on the same inputs"""
+    E, mu, rho = consts
     emu.set_fused(True)
     rng = np.random.default_rng(seed)
     Ws, bs = po.xavier_init(layers, rng)
     bs = [0.3 * rng.standard_normal(b.shape) for b in bs]
     flat = po.pack_params(Ws, bs).astype(np.float32)
-    X = po.collocation_points(n, LB, UB, rng)
+    X = po.collocation_points(n, lb, ub, rng)
     x, y, t = (X[:, k].astype(np.float32).copy() for k in range(3))
     tw = np.array([1, 2, 3, 1, 0.5, 1, 2.0]) / n
     sets_np = []
     for k, m in enumerate(n_side):
-        S = po.collocation_points(m, LB, UB, rng).astype(np.float32)
+        S = po.collocation_points(m, lb, ub, rng).astype(np.float32)
         tg = (0.1 * rng.standard_normal((7, m))).astype(np.float32) if k % 2 == 0 else None
         ow = [(1.0 + i) / max(m, 1) if i in ((0, 1), (0, 1, 2, 3), (5, 6))[k % 3] else 0.0 for i in range(7)]
         sets_np.append([np.ascontiguousarray(S[:, j]) for j in range(3)] + [tg, ow, np.full(8, np.nan, np.float32)])
@@ -762,13 +763,13 @@ def _step_case(emu, layers, n, n_side, prec, seed, with_adam):
             rows.append((sx.ctypes.data, sy.ctypes.data, st.ctypes.data, sx.size, 0 if tg is None else tg.ctypes.data, ow, lo.ctypes.data))
         emu.path_counts(reset=True)
         if mode == "step":
-            emu.wave2d_step(theta.ctypes.data, layers, x.ctypes.data, y.ctypes.data, t.ctypes.data, n, LB, UB, True, 2.5, 0.25, 1.0, True, tw, loss.ctypes.data,
+            emu.wave2d_step(theta.ctypes.data, layers, x.ctypes.data, y.ctypes.data, t.ctypes.data, n, lb, ub, True, E, mu, rho, True, tw, loss.ctypes.data,
                             rows, grad.ctypes.data, False, (m1.ctypes.data, v1.ctypes.data, 1e-3, 0.9, 0.999, 1e-8, 3) if with_adam else None, prec,
                             ws.ctypes.data, wsb)
         else:
-            emu.wave2d_loss_grad(theta.ctypes.data, layers, x.ctypes.data, y.ctypes.data, t.ctypes.data, n, LB, UB, True, 2.5, 0.25, 1.0, True, tw,
+            emu.wave2d_loss_grad(theta.ctypes.data, layers, x.ctypes.data, y.ctypes.data, t.ctypes.data, n, lb, ub, True, E, mu, rho, True, tw,
                                  loss.ctypes.data, grad.ctypes.data, False, prec, ws.ctypes.data, wsb)
-            emu.data_loss_grad_multi(theta.ctypes.data, layers, rows, LB, UB, True, grad.ctypes.data, True, prec, ws.ctypes.data, wsb)
+            emu.data_loss_grad_multi(theta.ctypes.data, layers, rows, lb, ub, True, grad.ctypes.data, True, prec, ws.ctypes.data, wsb)
             if with_adam:
                 emu.adam_step(theta.ctypes.data, m1.ctypes.data, v1.ctypes.data, grad.ctypes.data, theta.size, 1e-3, 3)
         out[mode] = dict(theta=theta, m=m1, v=v1, loss=loss[:7].copy(), grad=grad, side=[r[5][:7].copy() for r in sets_np], counts=emu.path_counts(reset=True))

@@ -269,3 +269,54 @@ def test_shard_as_holds_and_weights_one_ranks_share():
     np.testing.assert_allclose(parts[0] + parts[1], whole._buf.numpy(), rtol=2e-5, atol=1e-7)
     with pytest.raises(ValueError, match="collective"):
         DeepHPM(Collo, SRC, IC, UP, LAYERS, LB, UB, engine=OracleEngine(LAYERS), collective="ring", **kw)
+
+
+class _SteppingOracleEngine(OracleEngine):
+    """OracleEngine with HipEngine's one-call step (wave_step), so that DeepHPM takes that branch of its step too"""
+
+    def wave_step(self, params, x, y, t, lb, ub, normalize, term_weights, sets, grad_out, loss_out, E=2.5, mu=0.25, rho=1.0, plane_strain=True,
+                  accumulate=False, adam=None):
+        self.calls.append(("step", x.numel()))
+        self.wave_loss_grad(params, x, y, t, lb, ub, normalize, term_weights, E, mu, rho, plane_strain, grad_out=grad_out, accumulate=accumulate,
+                            loss_out=loss_out)
+        self.data_loss_grad_multi(params, sets, lb, ub, normalize, grad_out, accumulate=True)
+        if adam is not None:
+            m, v, lr, step = adam[:4]
+            self.adam_step(params, m, v, grad_out, lr, step)
+        return grad_out
+
+
+@pytest.mark.parametrize("step_call", [False, True])
+def test_material_constants_reach_the_engine(step_call):
+    """DeepHPM(E=, mu=, rho=) at constants where c1, c2, G, rho are pairwise distinct (set A): two Adam steps per block follow the oracle's
+    trajectory at THOSE constants, through the separate engine calls and through the one-call step -- and not the reference constants'"""
+    from tests._general_constants import CONSTS
+    E, mu, rho = CONSTS["A"]
+    Collo, SRC, IC, UP = small_sets(n=301)
+    eng = (_SteppingOracleEngine if step_call else OracleEngine)(LAYERS)
+    m = DeepHPM(Collo, SRC, IC, UP, LAYERS, LB, UB, engine=eng, verbose=False, seed=5, E=E, mu=mu, rho=rho)
+    th0 = m.theta.numpy().astype(np.float64).copy()
+    m.train(2, 1e-3, 3)
+    assert sum(c[0] == "step" for c in eng.calls) == (6 if step_call else 0)
+    replay = {}
+    for consts in ((E, mu, rho), (2.5, 0.25, 1.0)):
+        th, mm, vv = th0, np.zeros_like(th0), np.zeros_like(th0)
+        step = 0
+        for b in range(3):
+            s, e = int(b * 301 / 3), int((b + 1) * 301 / 3)
+            for _ in range(2):
+                _, g = po.wave_total_loss_grad(th, LAYERS, dict(collo=Collo[s:e], IC=IC, SRC=SRC), LB, UB, True, "infinite", *consts)
+                step += 1
+                th, mm, vv = po.adam_tf1_step(th, g, mm, vv, step, 1e-3)
+        replay[consts] = th
+    np.testing.assert_allclose(m.theta.numpy(), replay[(E, mu, rho)], rtol=1e-4, atol=1e-6)
+    assert np.abs(replay[(2.5, 0.25, 1.0)] - replay[(E, mu, rho)]).max() > 100 * 1e-6     # (the test has teeth)
+    # loss terms and gradient of a whole-batch evaluation at the trained weights
+    flat = m.theta.numpy().astype(np.float64)
+    terms, grad = po.wave_total_loss_grad(flat, LAYERS, dict(collo=Collo, IC=IC, SRC=SRC), LB, UB, True, "infinite", E, mu, rho)
+    m._loss_and_grad(0, Collo.shape[0])
+    P = m.n_params
+    tm = m._terms_from_sums(m._buf[P:].numpy().reshape(5, 8), Collo.shape[0])
+    for k in ("loss_f_uv", "loss_f_s", "loss_IC", "loss_SRC", "loss"):
+        assert abs(tm[k] - terms[k]) <= 1e-5 * max(1.0, abs(terms[k])), k
+    np.testing.assert_allclose(m._buf[:P].numpy(), grad, rtol=2e-4, atol=1e-7)

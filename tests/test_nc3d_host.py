@@ -90,3 +90,39 @@ def test_nc3d_data_parallel_two_ranks(tmp_path):
     np.testing.assert_allclose(z["theta0"], z["theta1"], rtol=0, atol=0)
     np.testing.assert_allclose(z["theta0"], m.theta.numpy(), rtol=2e-5, atol=2e-7)
     np.testing.assert_allclose(z["loss"], np.array(losses[4]), rtol=1e-4)
+
+
+def test_material_constants_reach_the_engine():
+    """NavierCauchy3D(E=, mu=, rho=) at set A (c1, c2, G, rho pairwise distinct): loss and gradient at those constants, before and after a
+    few Adam steps, against the oracle evaluated directly -- and not the reference constants'"""
+    from tests._general_constants import CONSTS
+    E, mu, rho = CONSTS["A"]
+    c, m = small(E=E, mu=mu, rho=rho)
+    lay, N, P = LOSS_LAYOUT_3D, 301, m.n_params
+
+    def total(th, consts):
+        tw = np.array([lay["f_uv"]] * 6 + [lay["f_s"]] * 6) / N
+        ss, g, _ = n3.nc3d_loss_grad(th, c["uv_layers"], *c["Collo"].T, c["lb"], c["ub"], True, *consts, term_weights=tw)
+        tot = (ss * tw).sum()
+        for name, A, colsel, tcols in (("IC", c["IC"], (0, 1, 2, 3, 4, 5), None), ("SRC", c["SRC"], (0, 1, 2), (4, 5, 6)), ("NB", c["TOP"], (8, 10, 11), None)):
+            ow = np.zeros(12)
+            ow[list(colsel)] = lay[name] / A.shape[0]
+            tg = None
+            if tcols:
+                tg = np.zeros((A.shape[0], 12))
+                tg[:, list(colsel)] = A[:, list(tcols)]
+            s2, g2, _ = n3.nc3d_data_loss_grad(th, c["uv_layers"], *A[:, :4].T, c["lb"], c["ub"], True, tg, ow)
+            g += g2
+            tot += (s2 * ow).sum()
+        return tot, g
+
+    for trained in (False, True):
+        if trained:
+            m.train(3, 2e-3, 1)
+        th = m.theta.numpy().astype(np.float64)
+        tot, g = total(th, (E, mu, rho))
+        m._loss_and_grad(0, N)
+        assert np.linalg.norm(m._buf[:P].numpy() - g) < 2e-6 * np.linalg.norm(g), trained
+        assert abs(m.getloss()[0] - tot) < 1e-5 * tot, trained
+        _, g_ref = total(th, (2.5, 0.25, 1.0))
+        assert np.linalg.norm(g_ref - g) > 0.1 * np.linalg.norm(g)          # (the test has teeth)

@@ -6,7 +6,9 @@ import pytest
 import torch
 
 from oracle import pinn_oracle as po
+from oracle import plate_oracle as pl
 from oracle.tf1_shaped import MinimalWave, TF1ShapedWave
+from tests._general_constants import CONSTS, LB2, UB2, distinct
 
 CASES = ["inf20s", "inf10s", "semi16s", "conf14s"]
 GOLDEN_CASES = CASES + ["wave64"]      # + the trained 8x64 net of tools/make_trained64.py (not reference data)
@@ -159,3 +161,92 @@ def test_large_golden_points_and_sums_reproduce(golden_dir):
     assert np.linalg.norm(grad - g["grad"]) <= 1e-12 * np.linalg.norm(g["grad"])
     assert np.allclose(np.linalg.norm(f, axis=0), g["f_colnorm"], rtol=1e-12)
     assert f[:m].shape == (m, 7)
+
+
+# ---- the physics heads at general constants (c1, c2, G, rho pairwise distinct; tests/_general_constants.py) ----------------------------
+_DIRS_2D = [(1.0, 0.0), (0.6, -0.8), (-0.3, 1.1)]
+
+
+def _wave_pts(n, seed):
+    return LB2 + (np.asarray(UB2) - LB2) * np.random.default_rng(seed).random((n, 3))
+
+
+def test_general_constant_sets_are_non_degenerate():
+    for E, mu, rho in CONSTS.values():
+        assert distinct(E, mu, rho, True) and distinct(E, mu, rho, False)
+
+
+@pytest.mark.parametrize("cs", sorted(CONSTS))
+@pytest.mark.parametrize("plane_strain", [True, False])
+@pytest.mark.parametrize("kind", ["P", "S"])
+def test_plane_waves_2d_are_residual_free(cs, plane_strain, kind):
+    """P (speed sqrt(c1/rho)) and S (sqrt(G/rho)) plane waves solve the 2-D head exactly, in several directions, in both laws;
+    the plane-stress wave solves the plate's five-stream head too.  Teeth: the S speed in a P wave (the P speed in an S wave), the
+    other law's coefficients, or another density leave an O(amplitude) residual."""
+    E, mu, rho = CONSTS[cs]
+    X = _wave_pts(400, 1)
+    c1, c2, G = po.hooke_coeffs(E, mu, plane_strain)
+    for k_dir in _DIRS_2D:
+        Y, dY = po.plane_wave_2d(kind, X, k_dir, E=E, mu=mu, rho=rho, plane_strain=plane_strain)
+        scale = max(np.abs(Y).max(), max(np.abs(d).max() for d in dY))
+        f = po.wave2d_residuals(Y, dY, E, mu, rho, plane_strain)
+        assert np.abs(f).max() < 1e-13 * scale, (k_dir, np.abs(f).max(0))
+        wrong_speed = np.sqrt((G if kind == "P" else c1) / rho)
+        Yw, dYw = po.plane_wave_2d(kind, X, k_dir, E=E, mu=mu, rho=rho, plane_strain=plane_strain, speed=wrong_speed)
+        assert np.abs(po.wave2d_residuals(Yw, dYw, E, mu, rho, plane_strain)[:, :2]).max() > 1e-2 * scale
+        assert np.abs(po.wave2d_residuals(Y, dY, E, mu, 1.3 * rho, plane_strain)[:, :2]).max() > 1e-2 * scale
+        if kind == "P":          # (an S wave strains e11 = -e22 and shears: c1 - c2 = 2 G in both laws, it solves both)
+            assert np.abs(po.wave2d_residuals(Y, dY, E, mu, rho, not plane_strain)[:, 4:]).max() > 1e-2 * scale
+        if plane_strain:
+            continue
+        F = po.plane_wave_plate(kind, X, k_dir, E=E, mu=mu, rho=rho)
+        fp = pl.plate_residuals(F, E, mu, rho)
+        assert np.abs(fp).max() < 1e-13 * scale, (k_dir, np.abs(fp).max(0))
+        if kind == "P":
+            Fs = po.plane_wave_plate(kind, X, k_dir, E=E, mu=mu, rho=rho, plane_strain=True)      # plane-strain c1 into the plane-stress head
+            assert np.abs(pl.plate_residuals(Fs, E, mu, rho)).max() > 1e-2 * scale
+        assert np.abs(pl.plate_residuals(F, E, mu, 1.3 * rho)[:, :2]).max() > 1e-2 * scale
+        Fw = po.plane_wave_plate(kind, X, k_dir, E=E, mu=mu, rho=rho, speed=wrong_speed)
+        assert np.abs(pl.plate_residuals(Fw, E, mu, rho)[:, :2]).max() > 1e-2 * scale
+
+
+@pytest.mark.parametrize("cs", sorted(CONSTS))
+def test_2d_adjoints_are_the_transpose_of_the_heads(cs):
+    """<g, f(Y + dY) - f(Y)> == <adjoint(g), dY> for the (affine) wave head in both laws and the plate head"""
+    E, mu, rho = CONSTS[cs]
+    rng = np.random.default_rng(17)
+    N = 60
+    for ps in (True, False):
+        Y, dY = rng.standard_normal((N, 7)), [rng.standard_normal((N, 7)) for _ in range(3)]
+        Yp, dYp = rng.standard_normal((N, 7)), [rng.standard_normal((N, 7)) for _ in range(3)]
+        g = rng.standard_normal((N, 7))
+        lhs = ((po.wave2d_residuals(Y + Yp, [a + b for a, b in zip(dY, dYp)], E, mu, rho, ps) - po.wave2d_residuals(Y, dY, E, mu, rho, ps)) * g).sum()
+        Yb, dYb = po.wave2d_residual_adjoint(g, E, mu, rho, ps)
+        rhs = (Yb * Yp).sum() + sum((a * b).sum() for a, b in zip(dYb, dYp))
+        assert abs(lhs - rhs) < 1e-12 * max(1.0, abs(lhs)), ps
+    F, Fp, g = rng.standard_normal((5, 5, N)), rng.standard_normal((5, 5, N)), rng.standard_normal((N, 5))
+    lhs = ((pl.plate_residuals(F + Fp, E, mu, rho) - pl.plate_residuals(F, E, mu, rho)) * g).sum()
+    rhs = (pl.plate_residual_adjoint(g, E, mu, rho) * Fp).sum()
+    assert abs(lhs - rhs) < 1e-12 * max(1.0, abs(lhs))
+
+
+def test_forward_tangent_equals_tf1_shaped_reverse_mode_general_constants():
+    """test_forward_tangent_equals_tf1_shaped_reverse_mode at constant set A on the anisotropic domain: both routes take E, mu, rho"""
+    E, mu, rho = CONSTS["A"]
+    rng = np.random.default_rng(4)
+    layers = [3, 24, 24, 24, 7]
+    Ws, bs = po.xavier_init(layers, rng)
+    bs = [0.2 * rng.standard_normal(b.shape) for b in bs]
+    X = po.collocation_points(257, LB2, UB2, rng, xc=11.0, yc=7.0)
+    tw = np.array([1.0] * 4 + [3.0] * 3) / 257
+    ss, g, f = po.wave2d_loss_grad(po.pack_params(Ws, bs), layers, X[:, 0], X[:, 1], X[:, 2], LB2, UB2, True, E, mu, rho, term_weights=tw)
+    _, g_ref, _ = po.wave2d_loss_grad(po.pack_params(Ws, bs), layers, X[:, 0], X[:, 1], X[:, 2], LB2, UB2, True, term_weights=tw)
+    assert np.linalg.norm(g - g_ref) > 0.1 * np.linalg.norm(g)           # the constants matter here
+    for cls in (TF1ShapedWave, MinimalWave):
+        m = cls(Ws, bs, LB2, UB2, True, E=E, mu=mu, rho=rho)
+        l_uv, l_s, gt, ft = m.flat_grad(X, 1.0, 3.0)
+        fr = torch.stack([r.reshape(-1) for r in ft], 1).detach().numpy()
+        assert abs(float(l_uv) - ss[:4].sum() / 257) < 1e-13 * max(1.0, ss[:4].sum() / 257)
+        assert abs(float(l_s) - ss[4:].sum() / 257) < 1e-13 * max(1.0, ss[4:].sum() / 257)
+        assert np.linalg.norm(fr - f) <= 1e-12 * np.linalg.norm(f)
+        assert np.linalg.norm(gt.numpy() - g) <= 1e-12 * np.linalg.norm(g)

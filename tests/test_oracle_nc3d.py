@@ -5,6 +5,7 @@ import pytest
 
 from oracle import nc3d_oracle as n3
 from oracle import pinn_oracle as po
+from tests._general_constants import CONSTS, LB3, UB3
 
 LB, UB = [0.0, 0.0, -20.0, 0.0], [30.0, 30.0, 0.0, 15.0]
 
@@ -93,3 +94,37 @@ def test_finite_difference_gradient():
         lp = (n3.nc3d_loss_grad(flat + e, layers, *X.T, LB, UB, True, want_grad=False)[0] * tw).sum()
         lm = (n3.nc3d_loss_grad(flat - e, layers, *X.T, LB, UB, True, want_grad=False)[0] * tw).sum()
         assert abs((lp - lm) / 2e-6 - g[i]) < 1e-6 * max(1.0, abs(g[i]))
+
+
+# ---- general constants (c1, c2, G, rho pairwise distinct; tests/_general_constants.py) and the anisotropic 3-D domain ----------------
+@pytest.mark.parametrize("cs", sorted(CONSTS))
+@pytest.mark.parametrize("kind,k_dir,pol", [("P", (1.0, 0.5, -0.3), None), ("S", (0.2, -1.0, 0.7), (1.0, 0.0, 0.0)), ("S", (0.0, 0.0, 1.0), (0.3, 1.0, 0.0))])
+def test_plane_waves_are_residual_free_general_constants(cs, kind, k_dir, pol):
+    """test_plane_waves_are_residual_free with the constants passed to the builder AND the head; teeth: another density, or G in the
+    place of c2, leaves an O(amplitude) residual"""
+    E, mu, rho = CONSTS[cs]
+    X = n3.halfspace_points(500, LB3, UB3, np.random.default_rng(3))
+    Y, dY = n3.plane_wave(kind, X, k_dir, pol, E=E, mu=mu, rho=rho)
+    scale = max(np.abs(Y).max(), max(np.abs(d).max() for d in dY))
+    assert np.abs(n3.nc3d_residuals(Y, dY, E, mu, rho)).max() < 1e-13 * scale
+    assert np.abs(n3.nc3d_residuals(Y, dY, E, mu, 1.3 * rho)[:, :3]).max() > 1e-2 * scale
+    if kind == "P":
+        c1, c2, G = n3.hooke3d(E, mu)
+        Yw, dYw = n3.plane_wave(kind, X, k_dir, pol, E=E, mu=mu, rho=rho * c1 / G)          # the S speed in a P wave
+        assert np.abs(n3.nc3d_residuals(Yw, dYw, E, mu, rho)[:, :3]).max() > 1e-2 * scale
+
+
+@pytest.mark.parametrize("cs", sorted(CONSTS))
+def test_adjoint_is_the_transpose_of_the_head_general_constants(cs):
+    E, mu, rho = CONSTS[cs]
+    rng = np.random.default_rng(8)
+    N = 50
+    Y, dY = rng.standard_normal((N, 12)), [rng.standard_normal((N, 12)) for _ in range(4)]
+    dYp, ddYp = rng.standard_normal((N, 12)), [rng.standard_normal((N, 12)) for _ in range(4)]
+    g = rng.standard_normal((N, 12))
+    f0 = n3.nc3d_residuals(Y, dY, E, mu, rho)
+    f1 = n3.nc3d_residuals(Y + dYp, [a + b for a, b in zip(dY, ddYp)], E, mu, rho)
+    Yb, dYb = n3.nc3d_residual_adjoint(g, E, mu, rho)
+    lhs = ((f1 - f0) * g).sum()
+    rhs = (Yb * dYp).sum() + sum((a * b).sum() for a, b in zip(dYb, ddYp))
+    assert abs(lhs - rhs) < 1e-10 * max(1.0, abs(lhs))
