@@ -52,7 +52,13 @@ enum {
                              the most sensitive reference net the worst per-layer multiple of fp32's own error moves 3.9 -> 4.6 of the tests' bound
                              of 6, elsewhere not at all); PINN_FLAG_STATE_FP16 drops the low parts altogether and is NOT parity-grade. */
     PINN_PREC_F16 = 2,    /* fp16 operands, one MFMA per product */
-    PINN_PREC_BF16X3 = 3, /* bf16 hi/lo split, three MFMAs per product (16-bit significand) */
+    PINN_PREC_BF16X3 = 3, /* bf16 hi/lo split, three MFMAs per product (16-bit significand).  As in PINN_PREC_F16X3 (2), the weight gradient
+                             of padded width 64 takes the layer states (four- and five-stream kernels: the adjoints too) as high parts only --
+                             here bf16 ones, 8 significant bits against fp16's 11: a random rounding noise c / sqrt(points) relative to the
+                             gradient, about 8x the f16x3 one.  Measured on an MI355X at fresh Xavier weights (n = 64 / 1 024 / 16 384,
+                             mean of four draws, tools/narrow_noise_study.py): c = 2.5e-3 for the four-stream wave head, 5.5e-3 for the one-stream value heads
+                             (pinn_data_loss_grad, the hole traction), 9e-3 for the five-stream plate head (f16x3: 3e-4 / 7e-4 / 1.1e-3);
+                             the two-kernel path and the wider layouts use both parts of both (1e-5). */
     PINN_PREC_FP32 = 4,   /* plain fp32 FMA arithmetic, no matrix pipe (the reference's own precision, INF:71-92): ~100x slower,
                              for parity checks; offered by every entry point (wave, data, fields, the plate family with its second
                              time derivative, the 4-input heads) */
