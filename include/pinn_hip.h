@@ -105,7 +105,9 @@ enum {
     PINN_HEAD_PLATE = 2,       /* pinn_plate2d_loss_grad: five streams (second time derivative) */
     PINN_HEAD_NC3D = 3,        /* pinn_nc3d_loss_grad: four inputs, five first-order streams */
     PINN_HEAD_NC3D_DATA = 4,   /* pinn_nc3d_data_loss_grad */
-    PINN_HEAD_STREAMS = 5      /* pinn_stream_loss_grad (the plate's pre-training losses) */
+    PINN_HEAD_STREAMS = 5,     /* pinn_stream_loss_grad (the plate's pre-training losses, one set per call): always the two-kernel path */
+    PINN_HEAD_STREAM_SETS = 6  /* pinn_stream_loss_grad_multi (all sets of a pre-training loss in one call): five streams; fused for 4 hidden layers
+                                  of padded width <= 64 in f16x3 (bf16x3: padded width 64), the two-kernel path for every other net */
 };
 enum {
     PINN_PATH_FUSED_REGISTERS = 1,   /* fused persistent kernel, tile state in registers (padded width <= 64) */
@@ -213,6 +215,39 @@ int pinn_stream_loss_grad(const float* params_flat, const int* layers, int n_lay
                           const float* targets, const float* weights,
                           float* loss_terms_out, float* grad_flat_out, int accumulate,
                           int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* All point sets of a pre-training loss in ONE call (loss_DIST: 2 sets, loss_PART: 5; PLATE:194-215):
+ *   loss = sum over sets k, streams s, outputs o of  sets[k].weights[s][o] * sum_n (Y[s][o][n] - sets[k].targets[s][o][n])^2
+ *   grad_flat_out (+)= d/dparams loss      (the gradient of the UNnormalised loss)
+ * The weights of ALL sets are normalised by ONE maximum, wmax = the largest |weights[s][o]| over every set of the call (outputs >= n_out do
+ * not count):
+ *   sets[k].loss_terms_out[o] = sum_s (sets[k].weights[s][o] / wmax) * sum_n (...)^2
+ * so the caller's loss is wmax * the sum of every reported number.  (pinn_stream_loss_grad normalises by its one set's own maximum.)
+ * An empty set (n == 0) reports zeros; n_sets <= PINN_MAX_STREAM_SETS.  A target row whose weight is 0 is not read.
+ * For 4 hidden layers of padded width <= 64 in a split mode the call is repack (skipped under PINN_FLAG_WEIGHTS_PACKED) | ONE persistent
+ * launch over all sets | ONE reduction (pinn_path_for(.., PINN_HEAD_STREAM_SETS, ws_bytes) == PINN_PATH_FUSED_REGISTERS, counted once).
+ * Every other case -- another depth or width, PINN_FLAG_TWO_KERNEL, pinn_debug_set_fused(0), an unaligned workspace -- runs the sets
+ * one after the other on pinn_stream_loss_grad's path (counted once per non-empty set) and returns the same quantities under the same
+ * normalisation; PINN_PREC_FP32 likewise; the non-split 16-bit modes return PINN_ERR_PRECISION.
+ * Workspace rule of the fused case: one scratch image per persistent workgroup behind the fixed part of the plan, 120 KB at padded width 32
+ * and 240 KB at 64.  The launch uses min(256, images, steps) workgroups, steps = sum_k ceil(n_k / 64), and is declined (the sets then run on
+ * the two-kernel path, same results) when the workspace holds fewer than min(64, steps) images.  pinn_min_workspace_bytes() holds 64 images
+ * for these nets, and pinn_workspace_bytes(layers, n_max, mode), n_max the largest set, does from n_max = 1500 points on (0.7 images per
+ * 16 points): pass the larger of the two, as the host classes do.  pinn_path_for does not know the step count: it answers
+ * PINN_PATH_FUSED_REGISTERS when the workspace it is given holds 64 images.
+ * The adjoint shift (PINN_ADJOINT_SHIFT) is ignored, as in pinn_stream_loss_grad: the reported sums carry the normalised weights. */
+#define PINN_MAX_STREAM_SETS 8
+typedef struct {
+    const float* x; const float* y; const float* t; int64_t n;
+    const float* targets;        /* SoA [5][n_out][n] or NULL (= 0) */
+    float weights[5][8];         /* per (stream, output); unused outputs 0 */
+    float* loss_terms_out;       /* device, >= n_out floats */
+} pinn_stream_set;
+int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int n_layers,
+                                const pinn_stream_set* sets, int n_sets,
+                                const double lb[3], const double ub[3], int normalize,
+                                float* grad_flat_out, int accumulate,
+                                int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
 /* The 16-bit operand modes run the reverse pass on adjoints  2 w_i f_i / max|w|  (fp16: |x| < 65504).  A residual that is
  * orders of magnitude above its trained size -- the first trial points of an L-BFGS line search far from the optimum, a stiff

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 PREC = {"bf16": 0, "f16x3": 1, "f16": 2, "bf16x3": 3, "fp32": 4}
-HEADS = {"wave": 0, "data": 1, "plate": 2, "nc3d": 3, "nc3d_data": 4, "streams": 5}      # PINN_HEAD_*
+HEADS = {"wave": 0, "data": 1, "plate": 2, "nc3d": 3, "nc3d_data": 4, "streams": 5, "stream_sets": 6}      # PINN_HEAD_*
 PATHS = {1: "fused-registers", 2: "fused-lds", 3: "two-kernel", 4: "fp32"}                  # PINN_PATH_*
 FLAG_WEIGHTS_PACKED = 0x100
 FLAG_TWO_KERNEL = 0x400            # PINN_FLAG_TWO_KERNEL: keep the call off the fused kernel (weights beyond its |w| <= 2047 format)
@@ -37,6 +37,15 @@ class PointSet(C.Structure):
     """pinn_point_set of include/pinn_hip.h"""
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("t", C.c_void_p), ("n", C.c_int64), ("targets", C.c_void_p),
                 ("out_weights", C.c_float * 8), ("loss_terms_out", C.c_void_p)]
+
+
+MAX_STREAM_SETS = 8                # PINN_MAX_STREAM_SETS
+
+
+class StreamSet(C.Structure):
+    """pinn_stream_set of include/pinn_hip.h"""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("t", C.c_void_p), ("n", C.c_int64), ("targets", C.c_void_p),
+                ("weights", (C.c_float * 8) * 5), ("loss_terms_out", C.c_void_p)]
 
 
 class AdamState(C.Structure):
@@ -112,6 +121,8 @@ class PinnLib:
         L.pinn_plate2d_traction_loss_grad.restype = i32
         L.pinn_stream_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
         L.pinn_stream_loss_grad.restype = i32
+        L.pinn_stream_loss_grad_multi.argtypes = [vp, pi32, i32, C.POINTER(StreamSet), i32, pf64, pf64, i32, vp, i32, i32, vp, sz, vp]
+        L.pinn_stream_loss_grad_multi.restype = i32
         L.pinn_nc3d_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, pf32, vp, vp, i32, i32, vp, sz, vp]
         L.pinn_nc3d_loss_grad.restype = i32
         L.pinn_nc3d_data_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
@@ -198,7 +209,7 @@ class PinnLib:
 
     def path_for(self, layers, precision, head: str = "wave", ws_bytes: int = 0) -> str:
         """pinn_path_for: 'fused-registers' | 'fused-lds' | 'two-kernel' | 'fp32' for a loss + gradient call of family ``head``
-        ('wave', 'data', 'plate', 'nc3d', 'nc3d_data', 'streams'); ``precision`` is a mode name or the full precision_mode word"""
+        ('wave', 'data', 'plate', 'nc3d', 'nc3d_data', 'streams', 'stream_sets'); ``precision`` is a mode name or the full precision_mode word"""
         mode = PREC[precision] if isinstance(precision, str) else int(precision)
         rc = int(self.lib.pinn_path_for(self._ints(layers), len(layers), mode, HEADS[head], int(ws_bytes)))
         if rc <= 0:
@@ -375,6 +386,19 @@ class PinnLib:
                                             int(bool(normalize)), targets, (C.c_float * len(w))(*w), loss_out, grad_out,
                                             int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
         self.check(rc, "pinn_stream_loss_grad")
+
+    def stream_loss_grad_multi(self, params, layers, sets, lb, ub, normalize, grad_out, accumulate, prec, ws, ws_bytes, stream=0):
+        """pinn_stream_loss_grad_multi.  sets: list of (x, y, t, n, targets_or_0, weights[5][<=8], loss_out) with device pointers as
+        integers; the reported sums of every set are normalised by the largest |weight| of the whole call."""
+        arr = (StreamSet * max(1, len(sets)))()
+        for k, (x, y, t, n, tg, w, lo) in enumerate(sets):
+            arr[k].x, arr[k].y, arr[k].t, arr[k].n, arr[k].targets, arr[k].loss_terms_out = x or None, y or None, t or None, int(n), tg or None, lo
+            for s_, row in enumerate(w):
+                for o, v in enumerate(row):
+                    arr[k].weights[s_][o] = float(v)
+        rc = self.lib.pinn_stream_loss_grad_multi(params, self._ints(layers), len(layers), arr, len(sets), self._d3(lb), self._d3(ub),
+                                                  int(bool(normalize)), grad_out, int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_stream_loss_grad_multi")
 
     # -- 3-D Navier-Cauchy extension (4 inputs x, y, z, t; 12 outputs) ---------------------------------------------
     def nc3d_loss_grad(self, params, layers, x, y, z, t, n, lb, ub, normalize, E, mu, rho, term_weights, loss_out, grad_out, accumulate,

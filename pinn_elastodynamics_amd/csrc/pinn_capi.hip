@@ -306,7 +306,7 @@ size_t pinn_workspace_bytes(const int* layers, int n_layers, int64_t n, int prec
 
 int pinn_path_for(const int* layers, int n_layers, int precision_mode, int head, size_t ws_bytes) {
     if (!layers) return PINN_ERR_NULL;
-    if (head < PINN_HEAD_WAVE || head > PINN_HEAD_STREAMS) return PINN_ERR_LAYERS;
+    if (head < PINN_HEAD_WAVE || head > PINN_HEAD_STREAM_SETS) return PINN_ERR_LAYERS;
     const int din = (head == PINN_HEAD_NC3D || head == PINN_HEAD_NC3D_DATA) ? 4 : 3;
     NetDesc net;
     int width = 0;
@@ -358,6 +358,7 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3) {
     float wmax = 0.0f;
     for (int i = 0; i < 5; ++i)
         for (int o = 0; o < 8; ++o) { const float v = c.w5[i][o] < 0 ? -c.w5[i][o] : c.w5[i][o]; if (v > wmax) wmax = v; }
+    if (c.w5_norm > 0.0f) wmax = c.w5_norm;      // (a set of pinn_stream_loss_grad_multi: the call's one maximum)
     for (int i = 0; i < 5; ++i)
         for (int o = 0; o < 8; ++o) { a.w5[i][o] = c.w5[i][o]; a.w5n[i][o] = wmax > 0.0f ? c.w5[i][o] / wmax : 0.0f; }
     a.targets = c.targets;
@@ -752,6 +753,66 @@ int pinn_stream_loss_grad(const float* params_flat, const int* layers, int n_lay
     if (n == 0) return empty_batch(c, c.net.nout);
     if (!impl) return fp32_call(c, HEAD_STREAMS, c.net.nout, 5);
     return impl->stream_loss_grad(c);
+}
+
+int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int n_layers, const pinn_stream_set* sets, int n_sets,
+                                const double lb[3], const double ub[3], int normalize, float* grad_flat_out, int accumulate, int precision_mode,
+                                void* workspace, size_t ws_bytes, void* stream) {
+    if (n_sets < 0 || n_sets > PINN_MAX_STREAM_SETS) return PINN_ERR_SIZE;
+    if (n_sets > 0 && !sets) return PINN_ERR_NULL;
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, nullptr, nullptr, nullptr, 0, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (!grad_flat_out) return PINN_ERR_NULL;
+    c.grad_out = grad_flat_out;
+    c.accumulate = accumulate;
+    c.n_ssets = n_sets;
+    float wmax = 0.0f;
+    for (int k = 0; k < n_sets; ++k) {
+        const pinn_stream_set& u = sets[k];
+        if (u.n < 0) return PINN_ERR_SIZE;
+        if (!u.loss_terms_out || (u.n > 0 && (!u.x || !u.y || !u.t))) return PINN_ERR_NULL;
+        StreamSet& ss = c.ssets[k];
+        ss.x = u.x;
+        ss.y = u.y;
+        ss.t = u.t;
+        ss.targets = u.targets;
+        ss.n = (long)u.n;
+        ss.loss_out = u.loss_terms_out;
+        for (int s = 0; s < 5; ++s)
+            for (int o = 0; o < 8; ++o) {
+                const float w = o < c.net.nout ? u.weights[s][o] : 0.0f;
+                ss.w[s][o] = w;
+                if ((w < 0 ? -w : w) > wmax) wmax = w < 0 ? -w : w;
+            }
+    }
+    if (impl) return impl->stream_sets_loss_grad(c);
+    // PINN_PREC_FP32: the sets one after the other, under the call's one normalisation
+    bool first = true;
+    for (int k = 0; k < n_sets; ++k) {
+        const StreamSet& ss = c.ssets[k];
+        if (ss.n <= 0) {
+            if ((rc = (int)hipMemsetAsync(ss.loss_out, 0, (size_t)c.net.nout * sizeof(float), c.stream))) return rc;
+            continue;
+        }
+        Call s = c;
+        s.n_ssets = 0;
+        s.x = ss.x;
+        s.y = ss.y;
+        s.t = ss.t;
+        s.n = ss.n;
+        s.aux = ss.targets;
+        for (int i = 0; i < 5; ++i)
+            for (int o = 0; o < 8; ++o) s.w5[i][o] = ss.w[i][o];
+        s.w5_norm = wmax;
+        s.loss_out = ss.loss_out;
+        s.accumulate = accumulate || !first;
+        if ((rc = fp32_call(s, HEAD_STREAMS, c.net.nout, 5))) return rc;
+        first = false;
+    }
+    if (first && !accumulate) return (int)hipMemsetAsync(grad_flat_out, 0, (size_t)c.net.nparams * sizeof(float), c.stream);
+    return PINN_OK;
 }
 
 // ---- 4-input family: the 3-D Navier-Cauchy extension (BASELINE.json configs[4]; not in the reference -- oracle/nc3d_oracle.py) ----

@@ -1276,6 +1276,58 @@ __global__ __launch_bounds__(256) void reduce_grad_loss_kernel(const float* part
     }
 }
 
+// The same epilogue for the stream-target sets of fused_sets_kernel (pinn_stream_loss_grad_multi): up to 8 sets, loss_part
+// [wave][slots][8] with set k in slot k.  A sibling, not a wider LossOuts: what the existing callers launch does not change.
+struct LossOuts8 { float* p[8]; };
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void reduce_grad_loss_sets_kernel(const float* partial, int nchunks, int nparams, float scale, float* grad,
+                                                                    int accumulate, const float* loss_part, long nwaves, int nterms, int nsets,
+                                                                    int slots, LossOuts8 loss_out, const int* wflags, int nflags) {
+    __shared__ int bad_weights;
+    if (threadIdx.x == 0) bad_weights = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < nflags; i += 256)
+        if (wflags[i]) bad_weights = 1;
+    __syncthreads();
+    const float poison = bad_weights ? __builtin_nanf("") : 0.0f;
+    const int grad_blocks = (int)gridDim.x - nsets;
+    if ((int)blockIdx.x >= grad_blocks) {
+        const int k = (int)blockIdx.x - grad_blocks;
+        const int term = threadIdx.x >> 5, sub = threadIdx.x & 31;
+        double s = 0.0;
+        if (term < nterms)
+            for (long w = sub; w < nwaves; w += 32) s += (double)loss_part[(w * slots + k) * 8 + term];
+        float v = (float)s;
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        v += __shfl_xor(v, 4);
+        v += __shfl_xor(v, 8);
+        v += __shfl_xor(v, 16);
+        if (sub == 0 && term < nterms && loss_out.p[k] != nullptr) loss_out.p[k][term] = v + poison;
+        return;
+    }
+    __shared__ float sub[4][64];
+    const int pl = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const long p = (long)blockIdx.x * 64 + pl;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    if (p < nparams) {
+        int cidx = sl;
+        for (; cidx + 12 < nchunks; cidx += 16) {
+            s0 += partial[(long)cidx * nparams + p];
+            s1 += partial[(long)(cidx + 4) * nparams + p];
+            s2 += partial[(long)(cidx + 8) * nparams + p];
+            s3 += partial[(long)(cidx + 12) * nparams + p];
+        }
+        for (; cidx < nchunks; cidx += 4) s0 += partial[(long)cidx * nparams + p];
+    }
+    sub[sl][pl] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (sl == 0 && p < nparams) {
+        const float s = (sub[0][pl] + sub[1][pl]) + (sub[2][pl] + sub[3][pl]);
+        grad[p] = (accumulate ? grad[p] : 0.0f) + scale * s + poison;
+    }
+}
+
 // Epilogue of fused_step_kernel (round 5): ONE launch reduces the per-workgroup partials of BOTH parts of the step launch -- A: the collocation
 // set (slot layout [wave][8]), B: the value-only side sets ([wave][FUSED_MAX_SETS][8]) -- in the order the two separate calls used to
 // (grad = scaleA * sumA, then += scaleB * sumB: the same bits), writes the 1 + nsets loss sums, and, if `adam.theta` is set, applies the TF1 Adam

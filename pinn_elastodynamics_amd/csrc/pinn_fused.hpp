@@ -110,6 +110,25 @@ __device__ __forceinline__ long fused_next_step(const FusedArgs& a, long step) {
     return (b & 1) ? a.nsteps : a.n_plain + ((b >> 3) * 4 + ((b & 7) >> 1));
 }
 
+// Stream-target sets (pinn_stream_loss_grad_multi: the plate's pre-training losses loss_DIST / loss_PART, PLATE:194-215): the table of the
+// five-stream kernel's stream-target head (Fused<.., HEADSEL = 1>).  Set k owns the workgroup steps [step0[k], step0[k+1]) and has its own points,
+// targets ([5][n_out][n] or nullptr = 0), 5 x 8 weights (normalised by the call's largest |w|) and loss slot; an empty set owns no step.
+// mask[k] bit (8 s + o): weight (s, o) is non-zero -- the head reads a target row and forms an adjoint only there (the IC set of loss_DIST has
+// 2 of 25 pairs).  The table is the second argument of fused_sets_kernel: it stays in the kernel-argument segment (memory) and the head
+// fetches the current set's entries with scalar loads, nothing of it is held in registers across a step.
+constexpr int FUSED_MAX_STREAM_SETS = 8;
+struct StreamSetTable {
+    int nsets;
+    long step0[FUSED_MAX_STREAM_SETS + 1];
+    const float* x[FUSED_MAX_STREAM_SETS];
+    const float* y[FUSED_MAX_STREAM_SETS];
+    const float* t[FUSED_MAX_STREAM_SETS];
+    const float* targets[FUSED_MAX_STREAM_SETS];
+    long n[FUSED_MAX_STREAM_SETS];
+    unsigned long long mask[FUSED_MAX_STREAM_SETS];
+    float w[FUSED_MAX_STREAM_SETS][5][8];
+};
+
 // A launch constant, made opaque at its point of use inside the step loop.  Otherwise the compiler hoists whatever is computed from
 // such constants alone (2 * term weight, the packed tangent seeds of the input state ...) out of the loop into registers it then has
 // to spill -- and a spill reload in the step is a full memory round trip (round-2 phase stamps: 3.5 k cycles in the residual head).
@@ -147,8 +166,12 @@ __device__ __forceinline__ void fused_stamp_wall(const FusedArgs& a, bool who, i
 // a 2^-12 state rounding that cancellation amplifies at trained weights (see STATE_LO below).  Not the default.
 // DIN_ = 4 (round 3): the 3-D Navier-Cauchy extension of BASELINE configs[4] -- inputs (x, y, z, t), five FIRST-order streams (value, x, y, z,
 // t), 12 outputs and the 3-D residual head (oracle/nc3d_oracle.py); built for the LDS-operand layout of padded width 128.
-template <class Op, int SPLIT, int WIDTH, int NL, int NS_ = 4, bool FASTSTATE = false, int DIN_ = 3>
+// HEADSEL = 1 (five streams, three inputs only): the stream-target head over a table of point sets (StreamSetTable) instead of the plate head --
+// chosen at compile time: the plate kernels' code does not change.
+template <class Op, int SPLIT, int WIDTH, int NL, int NS_ = 4, bool FASTSTATE = false, int DIN_ = 3, int HEADSEL = 0>
 struct Fused {
+    static constexpr bool SSETS = HEADSEL == 1;
+    static_assert(HEADSEL == 0 || (HEADSEL == 1 && NS_ == 5 && DIN_ == 3), "the stream-target head: five streams, three inputs");
     static constexpr int NS = NS_, WB = WIDTH / 16, KS = WIDTH / 32, NP = SPLIT == 3 ? 2 : 1, DIN = DIN_;
     // the XCD-aware step assignment (FusedArgs::n_plain) -- not in the 3-D instantiation: the most register-starved kernel of the file (785 spilled
     // SGPRs) took the three extra scalar values of the loop as +10 % launch time (25.2 against 22.3-23.3 ms per 1 M points, with the tail on or off)
@@ -218,8 +241,14 @@ struct Fused {
     static constexpr int CONST_BIAS_F = (NL - 1) * WIDTH + 16, CONST_F = CONST_BIAS_F + WIDTH * 4, CONST_B = CONST_F * 4;
     // (Five streams at width 64 fill the 160 KB with tensors alone: that instantiation reads the constants from memory.)
     static constexpr int BASE_SLOTS = WSLDS ? NL + 1 : (ONE_SLOT ? 1 : 2);
+    // WG_SLO (the stream-target head at padded width 32, all states in LDS): the weight gradient also multiplies the states' LOW parts -- a third
+    // MFMA per product, as in the LDS-operand layouts -- so that small point sets reach the two-kernel path's accuracy (with high parts only:
+    // a 2^-12 / sqrt(points) noise, 5.7e-5 on 2 x 64 points against 1.6e-7).  The low parts of the layer in hand sit in ONE more image slot
+    // per tile behind the NL + 1 state slots, filled by the chain wave in the layer's hand-off window (S_NL from its registers, S_L from
+    // the parked low-part records); 4 x (10 + 6 x 5) KB fill the LDS, so this layout reads its constants from memory.
+    static constexpr bool WG_SLO = SSETS && !LDSOP && KS == 1 && NP == 2 && !FASTSTATE;
     // (Four inputs: the first layer's rows are 32 bytes and read from memory wherever they are used -- q_first, wide_first --: no LDS copy.)
-    static constexpr bool CONST_LDS = DIN_ == 3 && TILES * (TENSOR_Z_B + BASE_SLOTS * IMG_B) + CONST_B <= 160 * 1024;
+    static constexpr bool CONST_LDS = !WG_SLO && DIN_ == 3 && TILES * (TENSOR_Z_B + BASE_SLOTS * IMG_B) + CONST_B <= 160 * 1024;
     static constexpr int CONST_USED = CONST_LDS ? CONST_B : 0;
     static constexpr bool SLDS = !LDSOP && 4 * (TENSOR_Z_B + (NL + 1) * IMG_B) + CONST_USED <= 160 * 1024;      // all 1-stream cases; 4 streams: 4x32 only
     // ZDB (round 4; the narrow four-stream layouts with parked states, i.e. the collocation kernel of the 8 x 64 / 4 x 64 nets): the WEIGHT
@@ -235,7 +264,7 @@ struct Fused {
     // (Also the plate's five-stream narrow layout, with seed scale 1: its residuals at fresh weights are thousands -- E = 20 -- and x 16 would put
     // the normalised seeds beyond fp16; the normalised scale alone has 8x of margin in the study.)
     static constexpr bool ZDB = !LDSOP && !SLDS && (NS_ == 4 || (NS_ == 5 && DIN_ == 3)) && KS == 2 && NP == 2;
-    static constexpr float ZDB_SEED_SCALE = NS_ == 4 ? 16.0f : 1.0f;      // host side: adjoint seeds x 16, gradient / 16 at the reduction (fused_launch)
+    static constexpr float ZDB_SEED_SCALE = (NS_ == 4 || SSETS) ? 16.0f : 1.0f;      // host side: adjoint seeds x 16, gradient / 16 at the reduction (fused_launch)
     static constexpr int ZNP = ZDB ? 1 : NP;                         // parts of an adjoint image in LDS
     // WGLO: the weight gradient also multiplies LOW parts (the adjoints' scaled low part; LDS-operand layouts: the states' too).  Off for ZDB
     // only.  (Round 4, measured and NOT adopted: high parts only in the LDS-operand layouts as well -- 8 x 80 6.2 -> 5.5 ms per 1 M points, but
@@ -249,7 +278,9 @@ struct Fused {
     // rounding does not average out as 1 / sqrt(points) of the RESULT.)
     static constexpr int ZBUF_B = NS * KS * 1024;                    // ZDB: one high-part adjoint image
     static __device__ __forceinline__ constexpr int zbuf(int L) { return ZDB ? (L & 1) * ZBUF_B : 0; }      // Z_L lives in buffer L & 1
-    static constexpr int S_SLOTS = SLDS ? NL + 1 : BASE_SLOTS;
+    static constexpr int S_SLOTS = SLDS ? NL + 1 + (WG_SLO ? 1 : 0) : BASE_SLOTS;
+    static constexpr int LO_SLOT = NL + 1;                          // WG_SLO: the low-part image of the layer in hand
+    static_assert(!WG_SLO || SLDS, "the low-part slot belongs to the all-states-in-LDS layout");
     static constexpr int WAVE_B = TENSOR_Z_B + S_SLOTS * IMG_B;
     static constexpr int CONST_OFF = TILES * WAVE_B;
     // S1_BY_WG (round 4; the four-stream narrow kernel that recomputes S_1 in the reverse, RECOMP1 below): the recomputation is the
@@ -418,7 +449,8 @@ struct Fused {
         __amdgpu_buffer_rsrc_t accr;      // this wave's in-memory running sums (STREAM_SUMS: the weight gradient loads / stores them pass by pass)
     };
     // DL >= 2: the LDS-DMA of S_{DL-1} rides along, a slice behind every group (see DmaJob)
-    template <int NA, int NBK, bool SLO = false, int DL = 0, int SSTR = KS * SP * 1024>
+    // SLO_OFF: where the low parts of a state record sit relative to its high parts (LDS-operand layouts: the next record; WG_SLO: the low-part slot)
+    template <int NA, int NBK, bool SLO = false, int DL = 0, int SSTR = KS * SP * 1024, int SLO_OFF = 1024>
     static __device__ __forceinline__ void wg_blocks(const char* s0, const char* s1, const char* z0, const char* z1, f32x4 (&acc)[NA][NBK],
                                                      float (&bias_out)[NBK], const DmaJob* job = nullptr) {
         auto dma_slice = [&](int g) {
@@ -444,7 +476,7 @@ struct Fused {
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
                 f.Ah[a] = sfrag(s0, s1, 2 * j * WAVE_B + st * SSTR + 8 * a);
-                if constexpr (SLO && WGLO) f.Al[a] = sfrag(s0, s1, 2 * j * WAVE_B + st * SSTR + 1024 + 8 * a);
+                if constexpr (SLO && WGLO) f.Al[a] = sfrag(s0, s1, 2 * j * WAVE_B + st * SSTR + SLO_OFF + 8 * a);
             }
 #pragma unroll
             for (int b = 0; b < NBK; ++b) {
@@ -868,6 +900,7 @@ struct Fused {
         const char* z0 = w.z0 + zbuf(L);           // (ZDB: Z_L sits in buffer L & 1 of the Z area)
         const char* z1 = w.z1 + zbuf(L);
         const int wi = quad >> 1, wo = quad & 1;
+        constexpr int LO_OFF = (LO_SLOT - slot_of(L)) * IMG_B;      // (WG_SLO)
         if constexpr (L == 0) {
             if (quad < WB) {
                 f32x4 t[1][1] = {{A.first}};
@@ -881,6 +914,7 @@ struct Fused {
                 f32x4 t[1][1] = {{A.last}};
                 float b[1];
                 if constexpr (TOP_IN_Z) wg_blocks<1, 1, false, 0, TOPZ_STRIDE>(w.z0 + TOPZ_OFF + img_block(quad), w.z1 + TOPZ_OFF + img_block(quad), z0, z1, t, b);
+                else if constexpr (WG_SLO) wg_blocks<1, 1, true, 0, KS * SP * 1024, LO_OFF>(s0 + img_block(quad), s1 + img_block(quad), z0, z1, t, b);
                 else wg_blocks<1, 1>(s0 + img_block(quad), s1 + img_block(quad), z0, z1, t, b);
                 A.last = t[0][0];
                 if (quad == 0) A.bias[NL] += b[0];
@@ -892,13 +926,13 @@ struct Fused {
                 for (int i = 0; i < IBW; ++i)
 #pragma unroll
                     for (int o = 0; o < OBW; ++o) pend[i][o] = f32x4{0.f, 0.f, 0.f, 0.f};
-                wg_blocks<IBW, OBW, false, DMA_L>(s0 + img_block(wi * IBW), s1 + img_block(wi * IBW), z0 + zimg_block(wo * OBW), z1 + zimg_block(wo * OBW), pend, b, &job);
+                wg_blocks<IBW, OBW, WG_SLO, DMA_L, KS * SP * 1024, WG_SLO ? LO_OFF : 1024>(s0 + img_block(wi * IBW), s1 + img_block(wi * IBW), z0 + zimg_block(wo * OBW), z1 + zimg_block(wo * OBW), pend, b, &job);
 #pragma unroll
                 for (int i = 0; i < IBW; ++i)
 #pragma unroll
                     for (int o = 0; o < OBW; ++o) pend[i][o] += ld[i][o];
             } else {
-                wg_blocks<IBW, OBW, false, DMA_L>(s0 + img_block(wi * IBW), s1 + img_block(wi * IBW), z0 + zimg_block(wo * OBW), z1 + zimg_block(wo * OBW), A.mid[L - 1], b, &job);
+                wg_blocks<IBW, OBW, WG_SLO, DMA_L, KS * SP * 1024, WG_SLO ? LO_OFF : 1024>(s0 + img_block(wi * IBW), s1 + img_block(wi * IBW), z0 + zimg_block(wo * OBW), z1 + zimg_block(wo * OBW), A.mid[L - 1], b, &job);
             }
             // one bias block per wave per layer: out-block wo*OBW + wi (OBW == 2) or wo (OBW == 1, waves with wi == 0)
             if (OBW == 1) { if (wi == 0) A.bias[L] += b[0]; }
@@ -1304,7 +1338,8 @@ struct Fused {
     // park store of the width-32 kernel, tests/test_isa_hazards.py: it lives in a base only the QUAD layouts have)
     struct CtxQuad { char* lds0; };                // the workgroup's LDS (uniform): tile t's tensors at + t * WAVE_B (a QUAD chain wave works on both tiles)
     struct CtxPlain {};
-    struct Ctx : std::conditional_t<QUAD, CtxQuad, CtxPlain> {       // wave-invariant addressing state of a chain wave
+    struct CtxSets { const StreamSetTable* sst; };  // SSETS: the launch's set table (kernel-argument segment)
+    struct Ctx : std::conditional_t<QUAD, CtxQuad, std::conditional_t<SSETS, CtxSets, CtxPlain>> {       // wave-invariant addressing state of a chain wave
         __amdgpu_buffer_rsrc_t frags, scr, bias, w0p;  // bias / w0p: only where the constants are not in LDS
         unsigned lane16;                           // lane * 16: the only VGPR offset of the fragment traffic
         unsigned imgoff;                           // this lane's (rotated) 16-byte record inside a fragment record block of an S image
@@ -1338,6 +1373,7 @@ struct Fused {
         }
         __device__ __forceinline__ char* imgZ() const { return tenZ + imgoff; }
         __device__ __forceinline__ char* imgS(int L) const { return tenZ + TENSOR_Z_B + slot_of(L) * IMG_B + imgoff; }
+        __device__ __forceinline__ char* imgLo() const { return tenZ + TENSOR_Z_B + LO_SLOT * IMG_B + imgoff; }      // (WG_SLO)
     };
 
     // chain-layout adjoint fragments (hi and scaled lo) -> this lane's records of the wave's Z image
@@ -1842,11 +1878,27 @@ struct Fused {
                 } else if constexpr (!RECOMP) lo_from_scratch<0>(x, L, sla);
             }
             constexpr bool ONE_BARRIER = ZDB && L <= NL - 2;   // Z_L is in its buffer already: written by the reverse step that produced it
+            // WG_SLO: S_L's parked low-part records (this lane's own stores of the forward) travel during the hand-off and go into the
+            // low-part slot between the two barriers, where no weight-gradient wave reads
+            [[maybe_unused]] u32x4 lorec[NS][KS];
+            if constexpr (WG_SLO && L >= 1) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+#pragma unroll
+                    for (int kk = 0; kk < KS; ++kk)
+                        lorec[s][kk] = __builtin_amdgcn_raw_buffer_load_b128(x.scr, x.imgoff, SCRATCH_LO + (L - 1) * IMG_B + (s * KS + kk) * 1024, 0);
+            }
             if constexpr (!ONE_BARRIER) {
                 hand_barrier();                                // previous layer's fragment reads are done
                 fused_stamp(a, x.tracer, 3 + 3 * (NL - L));
                 if constexpr (ZDB) put_zimage_hi<KS>(x.imgZ() + zbuf(L), Zc);
                 else put_zimage<KS>(x.imgZ(), Zc);
+                if constexpr (WG_SLO && L >= 1) {
+#pragma unroll
+                    for (int s = 0; s < NS; ++s)
+#pragma unroll
+                        for (int kk = 0; kk < KS; ++kk) *reinterpret_cast<u32x4*>(x.imgLo() + (s * KS + kk) * 1024) = lorec[s][kk];
+                }
             } else {
                 fused_stamp(a, x.tracer, 3 + 3 * (NL - L));
             }
@@ -2735,6 +2787,23 @@ struct Fused {
             adj[4][3] = -a.rho * g[0];
             adj[4][4] = -a.rho * g[1];
             adj[4][5] = -a.rho * g[2];
+        } else if constexpr (SSETS) {
+            // sum_{s,o} w[s][o] (Y[s][o] - target[s][o])^2 of the step's set (chain_kernel's HEAD_STREAMS, pinn_device.hpp); lsum[o] accumulates the
+            // weight-normalised sum over streams.  Only the pairs of the set's mask: a row whose weight is 0 is never read.
+            const StreamSetTable& T = *x.sst;
+            const float* tg = T.targets[set];
+            const long nn = T.n[set];
+            const unsigned long long m = T.mask[set];
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+#pragma unroll
+                for (int o = 0; o < NOG; ++o)
+                    if ((m >> (8 * s + o)) & 1ull) {
+                        const float w = T.w[set][s][o];
+                        const float d = Y[s][o] - (tg ? tg[((long)s * a.net.nout + o) * nn + pidx] : 0.0f);
+                        if (q == 0) lsum[o] += vm * w * d * d;
+                        adj[s][o] = (WG_HI ? 2.0f * ZDB_SEED_SCALE : 2.0f) * w * d * vm;      // (the seed scale of the fp16 adjoints: taken back at the reduction)
+                    }
         } else if constexpr (HEAD == HEAD_PLATE) {
             // composite F = P + D*N (PLATE:383-387) with product-rule derivatives, then net_f_sig PLATE:404-439
             // outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt); aux = [D|P][stream][field][n]
@@ -2890,6 +2959,12 @@ struct Fused {
                 for (int kk = 0; kk < KS; ++kk) *reinterpret_cast<u32x4*>(x.imgZ() + TOPZ_OFF + s * TOPZ_STRIDE + kk * 1024) = B[s][0][kk][0];
         } else {
             put_image<KS>(x.imgS(NL), B);
+            if constexpr (WG_SLO) {                 // S_NL's low parts, from the forward's registers
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+#pragma unroll
+                    for (int kk = 0; kk < KS; ++kk) *reinterpret_cast<u32x4*>(x.imgLo() + (s * KS + kk) * 1024) = B[s][0][kk][NP - 1];
+            }
         }
         hand_barrier();
         fused_stamp(a, x.tracer, 4);
@@ -2933,7 +3008,7 @@ struct Fused {
         for (int i = 0; i < LT; ++i) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, run[i]), x.scr, x.lane16 >> 2, LSUM_OFF + i * 256, 0);
     }
 
-    static __device__ __forceinline__ void chain_role(const FusedArgs& a, char* lds, int wave4, int lane, int c, int q) {
+    static __device__ __forceinline__ void chain_role(const FusedArgs& a, char* lds, int wave4, int lane, int c, int q, const StreamSetTable* sst = nullptr) {
         // LDSOP: two waves per tile (tile = wave & 1, half = wave >> 1); otherwise one wave per tile
         const int wave = LDSOP ? (wave4 & 1) : wave4, half = LDSOP ? (wave4 >> 1) : 0;
         const long gwave = (long)fused_bid(a) * TILES + wave;
@@ -2941,6 +3016,7 @@ struct Fused {
         x.init(a, lds, wave, lane, c, q);
         x.set_tile(a, gwave);
         x.tracer = fused_bid(a) == 0 && wave4 == 0 && lane == 0;
+        if constexpr (SSETS) x.sst = sst;
         constexpr int NSETS = NS == 1 ? FUSED_MAX_SETS : 1;
         float lsum[NSETS][LT];
 #pragma unroll
@@ -2960,12 +3036,40 @@ struct Fused {
         const bool launch_tracer = x.tracer;
         fused_stamp(a, launch_tracer, NS == 1 ? 122 : 124);
         fused_stamp_wall(a, launch_tracer, NS == 1 ? 118 : 120);
+        // SSETS: one set's sums at a time.  A workgroup's steps ascend and a set's steps are contiguous, so the sets come in order: when the
+        // set changes, the finished set's sums go to its slot of loss_part [wave][FUSED_MAX_STREAM_SETS][8] and the slots of the sets skipped
+        // in between get zeros -- every slot of the wave is written exactly once per launch, and eight sums are live, not eight per set.
+        [[maybe_unused]] int cur_set = -1;
+        [[maybe_unused]] auto sets_flush = [&](int next) {
+            if (cur_set >= 0) {
+#pragma unroll
+                for (int i = 0; i < LT; ++i) {
+                    float v = lsum[0][i];
+                    v += __shfl_xor(v, 1);
+                    v += __shfl_xor(v, 2);
+                    v += __shfl_xor(v, 4);
+                    v += __shfl_xor(v, 8);
+                    if (lane == 0) a.loss_part[(gwave * FUSED_MAX_STREAM_SETS + cur_set) * LT + i] = v;
+                    lsum[0][i] = 0.0f;
+                }
+            }
+            for (int k = cur_set + 1; k < next; ++k)
+                if (lane < LT) a.loss_part[(gwave * FUSED_MAX_STREAM_SETS + k) * LT + lane] = 0.0f;
+            cur_set = next;
+        };
         for (long step = fused_bid(a); step < a.nsteps; step = XCD_TAIL ? fused_next_step(a, step) : step + a.grid) {
             float xin[4];
             bool valid;
             long pidx;
             int set = 0;
-            if constexpr (NS == 1) {
+            if constexpr (SSETS) {
+                const StreamSetTable& T = *sst;
+#pragma unroll
+                for (int k = 1; k < FUSED_MAX_STREAM_SETS; ++k)
+                    if (k < T.nsets && step >= T.step0[k]) set = k;
+                if (set != cur_set) sets_flush(set);
+                load_inputs(a, T.x[set], T.y[set], T.t[set], nullptr, T.n[set], (step - T.step0[set]) * TILES + wave, c, xin, valid, pidx);
+            } else if constexpr (NS == 1) {
 #pragma unroll
                 for (int k = 1; k < FUSED_MAX_SETS; ++k)
                     if (k < a.nsets && step >= a.set_step0[k]) set = k;
@@ -3030,7 +3134,7 @@ struct Fused {
 #pragma unroll
                     for (int k = 0; k < NSETS; ++k)
 #pragma unroll
-                        for (int i = 0; i < LT; ++i) lsum[k][i] += (k == set) ? ls[i] : 0.0f;
+                        for (int i = 0; i < LT; ++i) lsum[k][i] += (SSETS || k == set) ? ls[i] : 0.0f;      // (SSETS: the one live set's sums)
                 }
                 reverse_tile(a, x, xin, B, ZL);
             }
@@ -3042,6 +3146,10 @@ struct Fused {
 #pragma unroll
                 for (int i = 0; i < LT; ++i) lsum[0][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(x.scr, x.lane16 >> 2, LSUM_OFF + i * 256, 0));
             }
+        }
+        if constexpr (SSETS) {
+            sets_flush(FUSED_MAX_STREAM_SETS);      // the last set's sums, zeros behind it
+            return;
         }
 #pragma unroll
         for (int k = 0; k < NSETS; ++k)
@@ -3056,7 +3164,8 @@ struct Fused {
             }
     }
 
-    static __device__ __forceinline__ void run(const FusedArgs& a, char* lds /* LDS_B bytes, 16-byte aligned: declared by the kernel */) {
+    static __device__ __forceinline__ void run(const FusedArgs& a, char* lds /* LDS_B bytes, 16-byte aligned: declared by the kernel */,
+                                               const StreamSetTable* sst = nullptr /* SSETS only */) {
         const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
         const int wave8 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));     // provably wave-uniform
         if constexpr (CONST_LDS) {
@@ -3074,7 +3183,8 @@ struct Fused {
             wgrad_role(a, lds, wave8 - 4, lane, c, q);
         } else {
             __builtin_amdgcn_s_setprio(2);          // the chain wave is the critical path of its SIMD: issue it first
-            chain_role(a, lds, wave8, lane, c, q);
+            if constexpr (SSETS) chain_role(a, lds, wave8, lane, c, q, sst);
+            else chain_role(a, lds, wave8, lane, c, q);
         }
     }
 };
@@ -3084,6 +3194,15 @@ __global__ __launch_bounds__(512) void fused_wave_kernel(const FusedArgs a) {
     typedef Fused<Op, SPLIT, WIDTH, NL, NS, FASTSTATE, DIN> F;
     __shared__ __attribute__((aligned(16))) char lds[F::LDS_B];
     F::run(a, lds);
+}
+
+// The point sets of a pre-training loss (loss_DIST: 2 sets, loss_PART: 5; PLATE:194-215) in ONE persistent launch: the five-stream roles of
+// fused_wave_kernel with the stream-target head, the sets' table as a second argument (StreamSetTable).
+template <class Op, int SPLIT, int WIDTH, int NL>
+__global__ __launch_bounds__(512) void fused_sets_kernel(const FusedArgs a, const StreamSetTable tab) {
+    typedef Fused<Op, SPLIT, WIDTH, NL, 5, false, 3, 1> F;
+    __shared__ __attribute__((aligned(16))) char lds[F::LDS_B];
+    F::run(a, lds, &tab);
 }
 
 // One training step's point sets in ONE persistent launch (round 5): workgroups [0, a4.grid) run the collocation set (four streams, the

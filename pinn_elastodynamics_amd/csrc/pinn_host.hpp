@@ -48,6 +48,13 @@ struct ProfRing {
     void end(int slot, hipStream_t st) { if (slot >= 0) hipEventRecord(ev[slot][1], st); }
 };
 
+struct StreamSet {              // one stream-target point set of pinn_stream_loss_grad_multi
+    const float *x, *y, *t, *targets;
+    long n;
+    float w[5][8];
+    float* loss_out;
+};
+
 struct Call {
     NetDesc net;
     const float* params;
@@ -75,6 +82,9 @@ struct Call {
     // plate / traction / stream-target heads
     const float* aux;
     float w5[5][8];
+    float w5_norm = 0.0f;      // > 0: the stream-target weights are normalised by this value instead of their own maximum (a set of pinn_stream_loss_grad_multi)
+    int n_ssets = 0;           // pinn_stream_loss_grad_multi: the call's sets
+    StreamSet ssets[PINN_MAX_STREAM_SETS];
     // optional per-kernel timing (host pointer, 4 floats: repack, chain, wgrad, reductions) -- makes the call synchronous
     float* prof_ms;
     ProfRing* ring;            // optional asynchronous launch timing (see ProfRing)
@@ -107,6 +117,7 @@ struct Impl {
     int (*traction_loss_grad)(const Call&);
     int (*stream_loss_grad)(const Call&);
     int (*streams)(const Call&);
+    int (*stream_sets_loss_grad)(const Call&);      // pinn_stream_loss_grad_multi
     // 4-input family (3-D Navier-Cauchy extension: value + 4 first-order streams, 12 outputs), split-precision variants only
     int (*nc3d_loss_grad)(const Call&);
     int (*nc3d_data_loss_grad)(const Call&);
@@ -340,6 +351,7 @@ struct Host {
             twmax = 0.0f;
             for (int i = 0; i < 5; ++i)
                 for (int o = 0; o < 8; ++o) { const float v = c.w5[i][o] < 0 ? -c.w5[i][o] : c.w5[i][o]; if (v > twmax) twmax = v; }
+            if (c.w5_norm > 0.0f) twmax = c.w5_norm;
             for (int i = 0; i < 5; ++i)
                 for (int o = 0; o < 8; ++o) a.w5[i][o] = twmax > 0.0f ? c.w5[i][o] / twmax : 0.0f;
         }
@@ -683,6 +695,9 @@ struct Host {
                 if (SPLIT != 3) return PINN_ERR_PRECISION;
                 return fused_has_3d() && net.nl == 10 && net.din == 4 && net.nout == 12 && enough(fused_images_3d<1>(net, ws_bytes)) ? PINN_PATH_FUSED_LDS : PINN_PATH_TWO_KERNEL;
             case PINN_HEAD_STREAMS: return SPLIT == 3 ? PINN_PATH_TWO_KERNEL : PINN_ERR_PRECISION;
+            case PINN_HEAD_STREAM_SETS:
+                if (SPLIT != 3) return PINN_ERR_PRECISION;
+                return sets_has() && net.nl == 4 && enough(sets_images(net, ws_bytes)) ? PINN_PATH_FUSED_REGISTERS : PINN_PATH_TWO_KERNEL;
             default: return PINN_ERR_LAYERS;
         }
     }
@@ -826,6 +841,157 @@ struct Host {
         if constexpr (SPLIT == 3) return fields_ns<5, HEAD_FIELDS>(c);
         return PINN_ERR_PRECISION;
     }
+
+    // ---- pinn_stream_loss_grad_multi: the stream-target sets of a pre-training loss in one launch of fused_sets_kernel
+    // compiled for 4 hidden layers of padded width <= 64 in the split modes (the reference's 4 x 20 distance / particular nets, PLATE:527-559)
+    static constexpr bool sets_has() { return SPLIT == 3 && WIDTH <= 64; }
+    // scratch images a workspace holds for it (the rule of try_fused_sets AND of pinn_path_for)
+    static long sets_images(const NetDesc& net, size_t ws_bytes) {
+        if constexpr (sets_has()) {
+            typedef Fused<Op, SPLIT, WIDTH, 4, 5, false, 3, 1> F;
+            Plan p;
+            plan_fixed<4>(net, 1, p);
+            const size_t per_wg = (size_t)F::TILES * F::SCRATCH_BYTES;
+            if (ws_bytes < p.fixed_end + per_wg) return 0;
+            return (long)((ws_bytes - p.fixed_end) / per_wg);
+        } else {
+            return 0;
+        }
+    }
+    static float sets_wmax(const Call& c) {
+        float wmax = 0.0f;
+        for (int k = 0; k < c.n_ssets; ++k)
+            for (int s = 0; s < 5; ++s)
+                for (int o = 0; o < 8; ++o) { const float v = c.ssets[k].w[s][o] < 0 ? -c.ssets[k].w[s][o] : c.ssets[k].w[s][o]; if (v > wmax) wmax = v; }
+        return wmax;
+    }
+    // returns 1 if the fused launch ran (rc in *out), 0 if it does not apply (the caller then runs the sets one by one)
+    static int try_fused_sets(const Call& c, float wmax, int* out) {
+        if constexpr (sets_has()) {
+            typedef Fused<Op, SPLIT, WIDTH, 4, 5, false, 3, 1> F;
+            static_assert(F::WG_ACC_BYTES <= FUSED_ACC_BYTES, "accumulator area of the plan");
+            static_assert((size_t)FUSED_GRID * F::TILES * FUSED_MAX_STREAM_SETS * 8 <= (size_t)MAX_BLOCKS * 4 * LOSS_SLOTS_3D, "loss partials of the plan");
+            static_assert(FUSED_MAX_STREAM_SETS == PINN_MAX_STREAM_SETS, "set table");
+            if (c.net.nl != 4 || c.prof_ms != nullptr) return 0;
+            if (((uintptr_t)c.ws & 255) != 0) return 0;
+            Plan p;
+            plan_fixed<4>(c.net, 1, p);
+            long grid = sets_images(c.net, c.ws_bytes);
+            if (grid == 0) return 0;
+            if (grid > FUSED_GRID) grid = FUSED_GRID;
+            if (g_fused_grid_cap > 0 && grid > g_fused_grid_cap) grid = g_fused_grid_cap;
+            StreamSetTable T;
+            LossOuts8 lo;
+            long s0 = 0;
+            for (int k = 0; k < FUSED_MAX_STREAM_SETS; ++k) {
+                const bool on = k < c.n_ssets && c.ssets[k].n > 0;
+                T.step0[k] = s0;
+                T.x[k] = on ? c.ssets[k].x : nullptr;
+                T.y[k] = on ? c.ssets[k].y : nullptr;
+                T.t[k] = on ? c.ssets[k].t : nullptr;
+                T.targets[k] = on ? c.ssets[k].targets : nullptr;
+                T.n[k] = on ? c.ssets[k].n : 0;
+                T.mask[k] = 0;
+                for (int s = 0; s < 5; ++s)
+                    for (int o = 0; o < 8; ++o) {
+                        const float w = on && o < c.net.nout && wmax > 0.0f ? c.ssets[k].w[s][o] / wmax : 0.0f;
+                        T.w[k][s][o] = w;
+                        if (w != 0.0f) T.mask[k] |= 1ull << (8 * s + o);
+                    }
+                lo.p[k] = k < c.n_ssets ? c.ssets[k].loss_out : nullptr;
+                if (on) s0 += (c.ssets[k].n + 16 * F::TILES - 1) / (16 * F::TILES);
+            }
+            T.step0[FUSED_MAX_STREAM_SETS] = s0;
+            T.nsets = c.n_ssets;
+            const long nsteps = s0;
+            if (nsteps == 0) return 0;
+            if (grid > nsteps) grid = nsteps;
+            if (grid < FUSED_MIN_GRID && grid < nsteps) return 0;      // (see FUSED_MIN_GRID)
+            int rc = repack(c, p);
+            if (rc) { *out = rc; return 1; }
+            char* b = static_cast<char*>(c.ws);
+            FusedArgs a;
+            a.net = c.net;
+            a.pw = packed(c, p);
+            a.pw.frags = reinterpret_cast<const u32x4*>(b + p.frags_fused);
+            a.frags_bytes = (unsigned)((size_t)FI::total(c.net.nl) * FUSED_PARTS * 64 * sizeof(u32x4));
+            a.x = a.y = a.t = a.z = nullptr;      // (the table's)
+            a.n = 0;
+            a.nsteps = nsteps;
+            for (int k = 0; k < 4; ++k) { a.sx[k] = c.sx[k]; a.ox[k] = c.ox[k]; }
+            a.c1 = a.c2 = a.G = a.rho = 0.0f;
+            for (int i = 0; i < 16; ++i) a.tw[i] = 0.0f;
+            a.targets = nullptr;
+            a.aux = nullptr;
+            a.nsets = 0;
+            for (int k = 0; k < 4; ++k) {
+                a.set_step0[k] = 0;
+                a.set_x[k] = a.set_y[k] = a.set_t[k] = a.set_z[k] = a.set_targets[k] = a.set_aux[k] = nullptr;
+                a.set_n[k] = 0;
+                a.set_head[k] = 0;
+                for (int i = 0; i < 16; ++i) a.set_tw[k][i] = 0.0f;
+            }
+            a.set_step0[4] = 0;
+            a.scratch = reinterpret_cast<u32x4*>(b + p.panels);
+            a.loss_part = reinterpret_cast<float*>(b + p.loss_part);
+            a.partial = reinterpret_cast<float*>(b + p.partial);
+            a.wg_acc = reinterpret_cast<u32x4*>(b + p.wg_acc);
+            a.dbg = nullptr;
+            a.block0 = 0;
+            a.grid = (int)grid;
+            a.n_plain = 0x7fffffffffffffffL;      // (no XCD tail: a workgroup's steps ascend by the grid, which the per-set sums rely on)
+            // the weights are only ever used normalised; where the weight gradient takes fp16 adjoints (Fused::ZDB) the head scales its seeds
+            // by ZDB_SEED_SCALE into the normal range and the reduction takes the factor back
+            float scale = wmax;
+            if constexpr (F::WG_HI) scale *= 1.0f / F::ZDB_SEED_SCALE;
+            const int ring_slot = c.ring ? c.ring->begin(c.stream, 5) : -1;
+            hipLaunchKernelGGL((fused_sets_kernel<Op, SPLIT, WIDTH, 4>), dim3((int)grid), dim3(512), 0, c.stream, a, T);
+            if (c.ring) c.ring->end(ring_slot, c.stream);
+            if ((rc = (int)hipGetLastError())) { *out = rc; return 1; }
+            hipLaunchKernelGGL((reduce_grad_loss_sets_kernel<0>), dim3((c.net.nparams + 63) / 64 + c.n_ssets), dim3(256), 0, c.stream, (const float*)a.partial,
+                               (int)grid, c.net.nparams, scale, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, c.net.nout, c.n_ssets,
+                               (int)FUSED_MAX_STREAM_SETS, lo, (const int*)(b + p.wflags), repack_blocks(c.net));
+            *out = (int)hipGetLastError();
+            ++g_path_counts[PINN_PATH_FUSED_REGISTERS];
+            return 1;
+        } else {
+            return 0;
+        }
+    }
+    static int stream_sets_loss_grad(const Call& c) {
+        if constexpr (SPLIT == 3) {
+            const float wmax = sets_wmax(c);
+            int rc = 0;
+            if (c.use_fused && try_fused_sets(c, wmax, &rc)) return rc;
+            // every other case: the sets one after the other on pinn_stream_loss_grad's path, under the call's one normalisation
+            bool first = true;
+            for (int k = 0; k < c.n_ssets; ++k) {
+                const StreamSet& ss = c.ssets[k];
+                if (ss.n <= 0) {
+                    if ((rc = (int)hipMemsetAsync(ss.loss_out, 0, (size_t)c.net.nout * sizeof(float), c.stream))) return rc;
+                    continue;
+                }
+                Call s = c;
+                s.n_ssets = 0;
+                s.x = ss.x;
+                s.y = ss.y;
+                s.t = ss.t;
+                s.n = ss.n;
+                s.aux = ss.targets;
+                for (int i = 0; i < 5; ++i)
+                    for (int o = 0; o < 8; ++o) s.w5[i][o] = ss.w[i][o];
+                s.w5_norm = wmax;
+                s.loss_out = ss.loss_out;
+                s.accumulate = c.accumulate || !first;
+                s.weights_packed = c.weights_packed || !first;
+                if ((rc = loss_grad<5, HEAD_STREAMS>(s, c.net.nout))) return rc;
+                first = false;
+            }
+            if (first && !c.accumulate) return (int)hipMemsetAsync(c.grad_out, 0, (size_t)c.net.nparams * sizeof(float), c.stream);
+            return 0;
+        }
+        return PINN_ERR_PRECISION;
+    }
     // 4-input family (two-kernel path; the fused kernel covers the reference's 3-input nets only)
     static int nc3d_loss_grad(const Call& c) {
         if constexpr (SPLIT == 3) {
@@ -850,7 +1016,7 @@ struct Host {
 
     static const Impl* impl() {
         static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
-                               &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams,
+                               &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
                                &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields};
         return &I;
     }

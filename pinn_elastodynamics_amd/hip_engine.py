@@ -94,8 +94,8 @@ class HipEngine:
             import warnings
             seen.add(head)
             warnings.warn(f"layers {self.layers} ({self.precision}, '{head}' calls) run on the two-kernel path (chain_kernel + wgrad_kernel): "
-                          f"2.3-5x slower than the fused persistent kernel, which is compiled for 4 or 8 hidden layers of width <= 64, 8 of width "
-                          f"<= 128, 6 of width <= 160 and the 10 x 128 3-D net -- or the workspace is too small for its scratch images "
+                          f"2.3-5x slower than the fused persistent kernel, which is compiled for 4 or 8 hidden layers of width <= 64 (the "
+                          f"'stream_sets' calls of the plate's pre-training: 4), 8 of width <= 128, 6 of width <= 160 and the 10 x 128 3-D net -- or the workspace is too small for its scratch images "
                           f"(pinn_path_for, include/pinn_hip.h)", RuntimeWarning, stacklevel=3)
 
     def _stream(self) -> int:
@@ -292,6 +292,29 @@ class HipEngine:
                                   weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate, self.precision, self._ws_ptr,
                                   self.ws_bytes, self._stream())
         return loss_out[:nout], grad_out
+
+    def stream_loss_grad_multi(self, params, sets, lb, ub, normalize, grad_out=None, accumulate=False):
+        """All stream-target sets of a pre-training loss in one library call (pinn_stream_loss_grad_multi).  sets: list of
+        (x, y, t, targets [5, n_out, n] or None, weights 5 x n_out, loss_out[>= n_out]).  The sums of set k land in its loss_out, normalised
+        by the largest |weight| of ALL sets; the gradient of the unnormalised loss goes to grad_out.  Returns grad_out."""
+        self._chk(params, self.n_params)
+        nout = self.layers[-1]
+        rows = []
+        for x, y, t, tg, w, lo in sets:
+            n = x.numel()
+            for v in (x, y, t):
+                self._chk(v, n)
+            if tg is not None:
+                self._chk(tg, 5 * nout * n)
+            assert lo.is_cuda and lo.dtype == torch.float32 and lo.is_contiguous() and lo.numel() >= nout
+            rows.append((x.data_ptr(), y.data_ptr(), t.data_ptr(), n, 0 if tg is None else tg.data_ptr(), w, lo.data_ptr()))
+        if grad_out is None:
+            grad_out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+            accumulate = False
+        self._chk(grad_out, self.n_params)
+        self.lib.stream_loss_grad_multi(params.data_ptr(), self.layers, rows, lb, ub, normalize, grad_out.data_ptr(), accumulate, self._mode(False),
+                                        self._ws_ptr, self.ws_bytes, self._stream())
+        return grad_out
 
     # ---- 3-D Navier-Cauchy extension (layers [4, H, ..., H, 12]; inputs x, y, z, t) -------------------------------------
     def nc3d_loss_grad(self, params, x, y, z, t, lb, ub, normalize, term_weights, E=2.5, mu=0.25, rho=1.0,

@@ -354,6 +354,20 @@ class PINN(NetApi):
     def _pretrain_loss_grad(self, key, sets):
         """sum over sets of mean-square terms (PLATE:194-215); returns (loss, grad) on the host."""
         eng, th = self.eng[key], self.theta[key]
+        if hasattr(eng, "stream_loss_grad_multi"):
+            # one library call for all sets (4 x 20 nets: repack | one persistent launch | one reduction) and one copy to the host:
+            # buf = [grad | 8 sums per set], the sums normalised by the call's largest weight
+            P, m = th.numel(), len(sets)
+            buf = self.__dict__.setdefault("_pre_buf", {}).get(key)
+            if buf is None or buf.numel() != P + 8 * m:
+                buf = self._pre_buf[key] = torch.zeros(P + 8 * m, dtype=torch.float32, device=self.device)
+            rows = [(x, y, t, tg, (w / n).tolist(), buf[P + 8 * k:P + 8 * k + 8]) for k, ((x, y, t), tg, w, n) in enumerate(sets)]
+            eng.stream_loss_grad_multi(th, rows, self.lb, self.ub, False, grad_out=buf[:P], accumulate=False)
+            host = buf.detach().cpu().numpy().astype(np.float64)
+            wmax = max(float(np.abs(w).max() / n) for _, _, w, n in sets)
+            nout = int(eng.layers[-1])
+            total = sum(host[P + 8 * k:P + 8 * k + nout].sum() for k in range(m))
+            return float(np.float32(wmax) * total), host[:P].copy()
         grad = torch.zeros_like(th)
         total = torch.zeros((), dtype=torch.float32, device=self.device)
         for (x, y, t), tg, w, n in sets:
