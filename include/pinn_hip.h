@@ -86,7 +86,9 @@ enum {
     PINN_ERR_SIZE = -5,        /* n < 0 (n == 0 is a valid empty batch: zero sums, zero / untouched gradient) */
     PINN_ERR_COLLECTIVE = -6,  /* pinn_p2p_*: not connected; a coarse-grained buffer across devices (pinn_p2p_connect); or a rank did not arrive within the
                                 * bounded wait of some call (pinn_p2p_set_timeout_ms, default 30 s) -- that call's buffer is then NaN on this rank */
-    PINN_ERR_RANGE = -7        /* pinn_wave2d_loss_grad_checked: gradient non-finite even on the two-kernel path with the reverse pass scaled by 2^-24 */
+    PINN_ERR_RANGE = -7,       /* pinn_wave2d_loss_grad_checked: gradient non-finite even on the two-kernel path with the reverse pass scaled by 2^-24 */
+    PINN_ERR_STATE = -8,       /* pinn_lbfgs_*: state buffer shorter than pinn_lbfgs_state_bytes, not 256-byte aligned, or initialised for other sizes */
+    PINN_ERR_HISTORY = -9      /* pinn_lbfgs_*: history outside 1 .. PINN_LBFGS_MAX_HISTORY */
 };
 
 /* Padded hidden width the kernels use for a real hidden width h (0 if unsupported). */
@@ -384,6 +386,66 @@ int pinn_nc3d_fields(const float* params_flat, const int* layers, int n_layers,
  * correction).  step is 1-based.  All arrays are length n_params, updated in place. */
 int pinn_adam_step(float* params_flat, float* m, float* v, const float* grad_flat, int64_t n_params,
                    double lr, double beta1, double beta2, double eps, int64_t step, void* stream);
+
+/* ---- L-BFGS on the device.  Replaces tf.contrib.opt.ScipyOptimizerInterface(method 'L-BFGS-B') of the reference's second stage -- INF:122-129
+ * (construction, options), INF:321-335 (train_bfgs), PLATE:220-247 (the three optimizers, 1000 x loss for the pre-training ones), PLATE:508-559 (the
+ * three train_bfgs*) -- without bounds (the reference passes none).  A stage is a stream of kernels:  evaluate | advance | evaluate | advance ...
+ * with no host round trip per evaluation; one advance is THREE launches whatever the history length (one pass over the history rows for every inner
+ * product, one workgroup for the scalar logic and the m x m triangular solves of the compact representation of Byrd, Nocedal and Schnabel in fp64,
+ * one pass that forms the direction and the next point).  All inner products accumulate in fp64 in a fixed order (no atomics): results are a
+ * deterministic function of the inputs, so data-parallel ranks that advance on the same all-reduced buffer keep bit-identical parameters.
+ *   State: ONE caller-owned device buffer, 256-byte aligned, of pinn_lbfgs_state_bytes bytes: the ring of pairs S[m][P], Y[m][P], x_k, g_k, d
+ *   (fp32), S^T Y, Y^T Y, S^T g, Y^T g, the line search and the stop tests (fp64), a ring of the last PINN_LBFGS_LOSS_RING losses, the record.
+ *   Loss: loss = sum_j loss_coeffs[j] * loss_sums[j] (j < n_sums <= PINN_LBFGS_MAX_SUMS), formed on the device in fp64; the gradient the optimizer
+ *   sees is grad_scale * grad_flat (PLATE:220,230: coefficients and gradient of the pre-training stages carry the factor 1000).
+ *   Line search: strong Wolfe with L-BFGS-B's constants (ftol 1e-3, gtol 0.9, xtol 0.1; More-Thuente's safeguarded interpolation), at most maxls
+ *   trials, first step min(1, 1/||g||), later 1.  A trial whose loss or gradient is not finite counts as too long and is cut back; it never enters
+ *   the history.  s_k is the difference of the two fp32 parameter vectors the loss kernels saw; a pair with s.y <= 2.2e-16 y.y is skipped.
+ *   Stop rules (scipy's): (f_k - f_k+1) / max(|f_k|, |f_k+1|, 1) <= ftol; max|g| <= gtol; maxiter; maxfun; line search failed (after one restart
+ *   along -g with an empty history); not finite at the start point; PINN_LBFGS_NONFINITE_GRAD: a trial whose LOSS satisfies the decrease condition
+ *   came back with a non-finite gradient -- the 16-bit reverse pass overflowed (PINN_ADJOINT_SHIFT): the caller raises the shift and starts again
+ *   from params_flat.  At a stop params_flat holds the last accepted point (the best one: every accepted step lowers the loss), and every
+ *   further call leaves every buffer bitwise unchanged.
+ *   pinn_lbfgs_advance   consumes the evaluation at params_flat (grad_flat, loss_sums) and writes the next point to evaluate into params_flat.
+ *                        Asynchronous.  16-byte loads when params_flat and grad_flat are 16-byte aligned, scalar ones otherwise; any n_params.
+ *   pinn_lbfgs_status    the ONE synchronising call: copies the record out.
+ *   pinn_lbfgs_read_losses   losses of the evaluations [first, first + count) (count <= PINN_LBFGS_LOSS_RING, of the last ring's worth) as doubles.
+ *   pinn_lbfgs_debug_read    tests: the current direction (n_params floats) and the held pairs, oldest first (max_pairs rows of n_params floats each;
+ *                            any output may be NULL); *pairs_out = pairs held.  Synchronous. */
+#define PINN_LBFGS_MAX_HISTORY 64
+#define PINN_LBFGS_MAX_SUMS 128
+#define PINN_LBFGS_LOSS_RING 1024
+enum {
+    PINN_LBFGS_RUNNING = 0,
+    PINN_LBFGS_GTOL = 1,             /* max|g| <= gtol */
+    PINN_LBFGS_FTOL = 2,             /* relative reduction of the loss <= ftol */
+    PINN_LBFGS_MAXITER = 3,
+    PINN_LBFGS_MAXFUN = 4,
+    PINN_LBFGS_LINESEARCH = 5,       /* no acceptable step within maxls trials, also not along -g */
+    PINN_LBFGS_NONFINITE_START = 6,  /* loss or gradient not finite at the first point */
+    PINN_LBFGS_NONFINITE_GRAD = 7    /* acceptable loss, non-finite gradient: raise the adjoint shift / leave the fused path, start again */
+};
+typedef struct pinn_lbfgs_options {
+    int history;                     /* pairs kept, 1 .. PINN_LBFGS_MAX_HISTORY (scipy: maxcor) */
+    int maxiter, maxfun, maxls;
+    double ftol, gtol;
+} pinn_lbfgs_options;
+typedef struct pinn_lbfgs_record {
+    int status;                      /* PINN_LBFGS_* */
+    int iterations, evaluations;
+    int pairs, skipped;              /* pairs held now; pairs skipped by the curvature rule so far */
+    int trials;                      /* of the current line search */
+    int64_t loss_pos;                /* losses written to the ring so far (== evaluations) */
+    double f, max_abs_grad, step;    /* at the last accepted point; the step that reached it */
+} pinn_lbfgs_record;
+size_t pinn_lbfgs_state_bytes(int64_t n_params, int history);      /* 0 for bad arguments */
+int pinn_lbfgs_init(void* state, size_t state_bytes, int64_t n_params, const pinn_lbfgs_options* options, const float* loss_coeffs /* host */,
+                    int n_sums, double grad_scale, void* stream);
+int pinn_lbfgs_advance(void* state, float* params_flat, const float* grad_flat, const float* loss_sums, void* stream);
+int pinn_lbfgs_status(const void* state, pinn_lbfgs_record* host_record, void* stream);
+int pinn_lbfgs_read_losses(const void* state, int64_t first, int64_t count, double* host_out, void* stream);
+int pinn_lbfgs_debug_read(const void* state, int64_t n_params, int history, float* direction_out, float* s_out, float* y_out, int max_pairs,
+                          int* pairs_out, void* stream);
 
 /* ---- Latency-floor all-reduce of the step's buffer [gradient | loss sums] (round 5; SURVEY sections 5 and 8e).  The message is ~119 KB:
  * latency-bound, so a ring or tree buys nothing.  One-shot: every rank WRITES its buffer into a slot of every peer's IPC-mapped receive buffer

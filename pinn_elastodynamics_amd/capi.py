@@ -59,6 +59,26 @@ class RangeState(C.Structure):
     _fields_ = [("adjoint_shift", C.c_int32), ("two_kernel", C.c_int32), ("attempts", C.c_int32), ("reserved", C.c_int32)]
 
 
+LBFGS_STATUS = {0: "running", 1: "gtol", 2: "ftol", 3: "maxiter", 4: "maxfun", 5: "linesearch", 6: "nonfinite_start", 7: "nonfinite_grad"}      # PINN_LBFGS_*
+LBFGS_MAX_HISTORY, LBFGS_MAX_SUMS, LBFGS_LOSS_RING = 64, 128, 1024
+
+
+class LbfgsOptions(C.Structure):
+    """pinn_lbfgs_options of include/pinn_hip.h"""
+    _fields_ = [("history", C.c_int), ("maxiter", C.c_int), ("maxfun", C.c_int), ("maxls", C.c_int), ("ftol", C.c_double), ("gtol", C.c_double)]
+
+
+class LbfgsRecord(C.Structure):
+    """pinn_lbfgs_record of include/pinn_hip.h"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("evaluations", C.c_int), ("pairs", C.c_int), ("skipped", C.c_int), ("trials", C.c_int),
+                ("loss_pos", C.c_int64), ("f", C.c_double), ("max_abs_grad", C.c_double), ("step", C.c_double)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["status_name"] = LBFGS_STATUS.get(self.status, "?")
+        return d
+
+
 class PinnLibError(RuntimeError):
     pass
 
@@ -131,6 +151,19 @@ class PinnLib:
         L.pinn_nc3d_fields.restype = i32
         L.pinn_adam_step.argtypes = [vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, vp]
         L.pinn_adam_step.restype = i32
+        if hasattr(L, "pinn_lbfgs_init"):              # (one-variant experiment builds of older trees do not have the device L-BFGS)
+            L.pinn_lbfgs_state_bytes.argtypes = [i64, i32]
+            L.pinn_lbfgs_state_bytes.restype = sz
+            L.pinn_lbfgs_init.argtypes = [vp, sz, i64, C.POINTER(LbfgsOptions), pf32, i32, f64, vp]
+            L.pinn_lbfgs_init.restype = i32
+            L.pinn_lbfgs_advance.argtypes = [vp, vp, vp, vp, vp]
+            L.pinn_lbfgs_advance.restype = i32
+            L.pinn_lbfgs_status.argtypes = [vp, C.POINTER(LbfgsRecord), vp]
+            L.pinn_lbfgs_status.restype = i32
+            L.pinn_lbfgs_read_losses.argtypes = [vp, i64, i64, pf64, vp]
+            L.pinn_lbfgs_read_losses.restype = i32
+            L.pinn_lbfgs_debug_read.argtypes = [vp, i64, i32, vp, vp, vp, i32, pi32, vp]
+            L.pinn_lbfgs_debug_read.restype = i32
         L.pinn_debug_set_profile_buffer.argtypes = [vp]
         L.pinn_debug_set_profile_buffer.restype = None
         if hasattr(L, "pinn_debug_set_xcd_bonus"):      # (tuning hook; experiment builds of older trees do not have it)
@@ -424,3 +457,41 @@ class PinnLib:
         rc = self.lib.pinn_adam_step(params, m, v, grad, int(n_params), float(lr), float(beta1), float(beta2), float(eps),
                                      int(step), stream)
         self.check(rc, "pinn_adam_step")
+
+    # -- L-BFGS on the device (pinn_lbfgs_*) ---------------------------------------------------------------------------
+    def lbfgs_state_bytes(self, n_params: int, history: int) -> int:
+        return int(self.lib.pinn_lbfgs_state_bytes(int(n_params), int(history)))
+
+    def lbfgs_init(self, state, state_bytes, n_params, options: dict, loss_coeffs, grad_scale=1.0, stream=0):
+        """pinn_lbfgs_init.  options: scipy's names (maxcor, maxiter, maxfun, maxls, ftol, gtol); loss = sum_j loss_coeffs[j] * sums[j]."""
+        o = LbfgsOptions(int(options.get("maxcor", 10)), int(options.get("maxiter", 15000)), int(options.get("maxfun", 15000)), int(options.get("maxls", 20)),
+                         float(options.get("ftol", 2.220446049250313e-09)), float(options.get("gtol", 1e-5)))
+        c = [float(v) for v in loss_coeffs]
+        self.check(self.lib.pinn_lbfgs_init(state or None, int(state_bytes), int(n_params), C.byref(o), (C.c_float * max(1, len(c)))(*c), len(c),
+                                            float(grad_scale), stream), "pinn_lbfgs_init")
+
+    def lbfgs_advance(self, state, params, grad, sums, stream=0):
+        self.check(self.lib.pinn_lbfgs_advance(state or None, params or None, grad or None, sums or None, stream), "pinn_lbfgs_advance")
+
+    def lbfgs_status(self, state, stream=0) -> dict:
+        """pinn_lbfgs_status (synchronises the stream): the record as a dict, with 'status_name' from LBFGS_STATUS"""
+        r = LbfgsRecord()
+        self.check(self.lib.pinn_lbfgs_status(state or None, C.byref(r), stream), "pinn_lbfgs_status")
+        return r.as_dict()
+
+    def lbfgs_read_losses(self, state, first: int, count: int, stream=0):
+        """losses of the evaluations [first, first + count) as a list of floats (synchronises)"""
+        out = (C.c_double * max(1, int(count)))()
+        self.check(self.lib.pinn_lbfgs_read_losses(state or None, int(first), int(count), out, stream), "pinn_lbfgs_read_losses")
+        return [float(v) for v in out[:int(count)]]
+
+    def lbfgs_debug_read(self, state, n_params: int, history: int, stream=0):
+        """(direction [P], S [pairs, P], Y [pairs, P]) as numpy arrays, pairs oldest first (pinn_lbfgs_debug_read; tests)"""
+        import numpy as _np
+        d = _np.zeros(int(n_params), dtype=_np.float32)
+        S = _np.zeros((int(history), int(n_params)), dtype=_np.float32)
+        Y = _np.zeros_like(S)
+        n = C.c_int(0)
+        self.check(self.lib.pinn_lbfgs_debug_read(state or None, int(n_params), int(history), d.ctypes.data, S.ctypes.data, Y.ctypes.data, int(history),
+                                                  C.byref(n), stream), "pinn_lbfgs_debug_read")
+        return d, S[:n.value].copy(), Y[:n.value].copy()

@@ -2,6 +2,7 @@
 // decoding into pinn::Call, and dispatch to the kernel family for (precision_mode, hidden width).
 #include "pinn_host.hpp"
 #include "pinn_fp32.hpp"
+#include "pinn_lbfgs.hpp"
 
 #ifndef PINN_VARIANTS_DEF
 #define PINN_VARIANTS_DEF "pinn_variants.def"     // experiments (tools/exp_build.sh) build a one-variant library
@@ -229,6 +230,8 @@ const char* pinn_error_string(int code) {
         case PINN_ERR_WORKSPACE: return "workspace too small or not 256-byte aligned";
         case PINN_ERR_SIZE: return "n must not be negative";
         case PINN_ERR_COLLECTIVE: return "p2p collective: not connected, a coarse-grained buffer across devices, or a rank did not arrive within the bounded wait (the call failed as a whole: buffer NaN, no Adam update)";
+        case PINN_ERR_STATE: return "L-BFGS state buffer too small, not 256-byte aligned, or not initialised for these sizes (pinn_lbfgs_state_bytes)";
+        case PINN_ERR_HISTORY: return "L-BFGS history must be 1..64 pairs";
         case PINN_ERR_RANGE: return "gradient non-finite even on the two-kernel path with the reverse pass scaled by 2^-24 (pinn_wave2d_loss_grad_checked)";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
     }
@@ -960,6 +963,82 @@ int pinn_wave2d_loss_grad_checked(const float* params_flat, const int* layers, i
         state->adjoint_shift = state->adjoint_shift + 4 > 24 ? 24 : state->adjoint_shift + 4;
     }
     return PINN_ERR_RANGE;
+}
+
+// ---- L-BFGS on the device (pinn_lbfgs.hpp) ----------------------------------------------------------------------------------------------------
+static_assert(sizeof(pinn_lbfgs_record) == sizeof(pinn::lbfgs::Record), "pinn_lbfgs_record mirrors the head of the device state");
+static_assert(PINN_LBFGS_MAX_HISTORY == pinn::lbfgs::MAX_M && PINN_LBFGS_MAX_SUMS == pinn::lbfgs::MAX_SUMS && PINN_LBFGS_LOSS_RING == pinn::lbfgs::RING, "");
+
+size_t pinn_lbfgs_state_bytes(int64_t n_params, int history) {
+    if (n_params < 1 || history < 1 || history > pinn::lbfgs::MAX_M) return 0;
+    return pinn::lbfgs::make_layout(n_params, history).total;
+}
+
+int pinn_lbfgs_init(void* state, size_t state_bytes, int64_t n_params, const pinn_lbfgs_options* options, const float* loss_coeffs, int n_sums,
+                    double grad_scale, void* stream) {
+    if (!state || !options || !loss_coeffs) return PINN_ERR_NULL;
+    if (n_params < 1 || n_sums < 1 || n_sums > pinn::lbfgs::MAX_SUMS || options->maxiter < 0 || options->maxfun < 1 || options->maxls < 1) return PINN_ERR_SIZE;
+    if (options->history < 1 || options->history > pinn::lbfgs::MAX_M) return PINN_ERR_HISTORY;
+    if ((reinterpret_cast<uintptr_t>(state) & 255) != 0 || state_bytes < pinn_lbfgs_state_bytes(n_params, options->history)) return PINN_ERR_STATE;
+    pinn::lbfgs::InitArgs a;
+    a.P = n_params; a.m = options->history; a.n_sums = n_sums; a.maxiter = options->maxiter; a.maxfun = options->maxfun; a.maxls = options->maxls;
+    a.grad_scale = (float)grad_scale; a.ftol = options->ftol; a.gtol = options->gtol;
+    for (int j = 0; j < pinn::lbfgs::MAX_SUMS; ++j) a.coeff[j] = j < n_sums ? loss_coeffs[j] : 0.0f;
+    return pinn::lbfgs::enqueue_init(state, a, pinn_lbfgs_state_bytes(n_params, options->history), static_cast<hipStream_t>(stream));
+}
+
+int pinn_lbfgs_advance(void* state, float* params_flat, const float* grad_flat, const float* loss_sums, void* stream) {
+    if (!state || !params_flat || !grad_flat || !loss_sums) return PINN_ERR_NULL;
+    if ((reinterpret_cast<uintptr_t>(state) & 255) != 0) return PINN_ERR_STATE;
+    return pinn::lbfgs::enqueue_advance(state, params_flat, grad_flat, loss_sums, static_cast<hipStream_t>(stream));
+}
+
+int pinn_lbfgs_status(const void* state, pinn_lbfgs_record* host_record, void* stream) {
+    if (!state || !host_record) return PINN_ERR_NULL;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = (int)hipMemcpyAsync(host_record, state, sizeof(pinn_lbfgs_record), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    return (int)hipStreamSynchronize(st);
+}
+
+int pinn_lbfgs_read_losses(const void* state, int64_t first, int64_t count, double* host_out, void* stream) {
+    if (!state || !host_out) return PINN_ERR_NULL;
+    if (first < 0 || count < 0 || count > pinn::lbfgs::RING) return PINN_ERR_SIZE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const double* ring = reinterpret_cast<const double*>(static_cast<const char*>(state) + pinn::lbfgs::make_layout(1, 1).ring);      // (the ring sits in front of the sized part)
+    int64_t done = 0;
+    while (done < count) {
+        const int64_t at = (first + done) % pinn::lbfgs::RING;
+        const int64_t run = count - done < pinn::lbfgs::RING - at ? count - done : pinn::lbfgs::RING - at;
+        int rc = (int)hipMemcpyAsync(host_out + done, ring + at, (size_t)run * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (rc) return rc;
+        done += run;
+    }
+    return (int)hipStreamSynchronize(st);
+}
+
+int pinn_lbfgs_debug_read(const void* state, int64_t n_params, int history, float* direction_out, float* s_out, float* y_out, int max_pairs,
+                          int* pairs_out, void* stream) {
+    if (!state || !pairs_out) return PINN_ERR_NULL;
+    if (n_params < 1 || max_pairs < 0) return PINN_ERR_SIZE;
+    if (history < 1 || history > pinn::lbfgs::MAX_M) return PINN_ERR_HISTORY;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    pinn::lbfgs::Header hd;
+    int rc = (int)hipMemcpyAsync(&hd, state, sizeof(hd), hipMemcpyDeviceToHost, st);
+    if (!rc) rc = (int)hipStreamSynchronize(st);
+    if (rc) return rc;
+    if (hd.P != n_params || hd.m != history) return PINN_ERR_STATE;
+    const pinn::lbfgs::Layout L = pinn::lbfgs::make_layout(n_params, history);
+    const char* base = static_cast<const char*>(state);
+    if (direction_out && (rc = (int)hipMemcpyAsync(direction_out, base + L.d, (size_t)n_params * 4, hipMemcpyDeviceToHost, st))) return rc;
+    const int n = hd.rec.pairs < max_pairs ? hd.rec.pairs : max_pairs, first = hd.rec.pairs == hd.m ? hd.head : 0;
+    for (int k = 0; k < n; ++k) {                        // oldest first; with max_pairs < pairs held, the oldest max_pairs
+        const size_t row = (size_t)((first + k) % hd.m) * L.stride * 4;
+        if (s_out && (rc = (int)hipMemcpyAsync(s_out + (size_t)k * n_params, base + L.S + row, (size_t)n_params * 4, hipMemcpyDeviceToHost, st))) return rc;
+        if (y_out && (rc = (int)hipMemcpyAsync(y_out + (size_t)k * n_params, base + L.Y + row, (size_t)n_params * 4, hipMemcpyDeviceToHost, st))) return rc;
+    }
+    *pairs_out = hd.rec.pairs;
+    return (int)hipStreamSynchronize(st);
 }
 
 }  // extern "C"

@@ -174,6 +174,87 @@ def lbfgs_on_device(theta, loss_and_grad, options, callback=None):
     return stats
 
 
+BFGS_BACKENDS = ("scipy", "torch", "hip")
+
+
+def check_backend(backend):
+    if backend not in BFGS_BACKENDS:
+        raise ValueError(f"backend must be one of {BFGS_BACKENDS}, not {backend!r}")
+
+
+class LbfgsResult(dict):
+    """What a device L-BFGS stage returns: fun, nit, nfev, status, message, success -- the fields of scipy's OptimizeResult a caller of
+    train_bfgs looks at (the parameters stay on the device, in the model's theta)."""
+    __getattr__ = dict.get
+
+
+_LBFGS_MESSAGES = {1: "CONVERGENCE: max|g| <= gtol", 2: "CONVERGENCE: relative reduction of f <= ftol", 3: "STOP: total no. of iterations reached limit",
+                   4: "STOP: total no. of f and g evaluations reached limit", 5: "ABNORMAL: line search failed",
+                   6: "ABNORMAL: loss or gradient not finite at the start point", 7: "ABNORMAL: gradient not finite at an acceptable point"}
+
+
+def lbfgs_hip(engine, theta, evaluate, n_params, loss_coeffs, options, callback=None, grad_scale=1.0, loss_scale=1.0, block=16, check=None,
+              shift_state=None, ladder=True, what="this stage"):
+    """The L-BFGS stage as a stream of kernels (``backend="hip"``): the library's own optimizer (pinn_lbfgs_*, include/pinn_hip.h: compact-form
+    direction, strong-Wolfe line search and scipy's stop rules, all on the device) behind the same loss kernels.  ``evaluate()`` enqueues the
+    loss + gradient kernels at ``theta`` and returns the device buffer [grad (n_params) | sums]; the loss the optimizer sees is
+    ``sum_j loss_coeffs[j] * sums[j]`` and its gradient ``grad_scale * grad``.  Nothing synchronises per evaluation: *evaluate -> advance* is
+    enqueued in blocks of ``block`` evaluations (``options["block"]`` overrides), the status is read ONCE per block, and the block's losses come
+    out of the device's loss ring -- so ``callback(loss / loss_scale)`` still fires once per evaluation, in order, but in BATCHES of up to
+    ``block`` calls, after the block has run.  When the status says stop, nothing more is enqueued (the calls of a block that were already behind
+    the stop change nothing); ``theta`` then holds the last accepted point, which is the best one.  ``check``: called at every status read (the
+    model classes pass their collective's status check).  A stop with a non-finite gradient climbs the range ladder of
+    evaluate_with_finite_gradient (leave the fused path for an out-of-range weight, else adjoint shift + 4) and starts again from the last
+    accepted point with an empty history and what is left of maxiter / maxfun; with ``shift_state`` (the model's bookkeeping dict) the shift is
+    lowered again as the loss falls (relax_adjoint_shift, at every status read -- once per block instead of once per evaluation).
+    ``ladder=False``: the evaluation has no range ladder (the plate's pre-training losses ignore the adjoint shift): a non-finite loss or gradient
+    raises FloatingPointError at once, naming ``what``.  Returns an LbfgsResult (fun, nit, nfev, status, message)."""
+    opts = dict(options)
+    block = max(1, min(int(opts.pop("block", block)), 1024))
+    maxfun, maxiter = int(opts.get("maxfun", 15000)), int(opts.get("maxiter", 15000))
+    opts.setdefault("gtol", 1e-5)                        # scipy's default pgtol (the reference does not set it)
+    state = engine.lbfgs_state(n_params, int(opts.get("maxcor", 10)))
+    nfev = nit = 0
+    while True:
+        engine.lbfgs_init(state, dict(opts, maxfun=max(1, maxfun - nfev), maxiter=max(0, maxiter - nit)), loss_coeffs, grad_scale)
+        seen = 0
+        while True:
+            for _ in range(max(1, min(block, maxfun - nfev - seen))):
+                buf = evaluate()
+                engine.lbfgs_advance(state, theta, buf[:n_params], buf[n_params:])
+            rec = engine.lbfgs_status(state)
+            if check is not None:
+                check()
+            if callback is not None:
+                for f in engine.lbfgs_losses(state, seen, rec["loss_pos"] - seen):
+                    callback(f / loss_scale)
+            seen = rec["loss_pos"]
+            if shift_state is not None and np.isfinite(rec["f"]):
+                relax_adjoint_shift(engine, rec["f"] / loss_scale, shift_state)
+            if rec["status"] != 0:
+                break
+        nfev += rec["evaluations"]
+        nit += rec["iterations"]
+        if rec["status"] in (6, 7) and not ladder:
+            raise FloatingPointError(f"{what} produced a non-finite loss or gradient (loss = {rec['f'] / loss_scale}); "
+                                     f"restart from other weights or use precision='bf16x3'")
+        if rec["status"] in (6, 7):
+            leave = getattr(engine, "leave_fused_path_if_weights_out_of_range", None)
+            if leave is not None and leave(theta):
+                pass
+            elif engine.adjoint_shift < 24:
+                engine.adjoint_shift = min(engine.adjoint_shift + 4, 24)
+                if shift_state is not None:
+                    shift_state["raised_at"] = None
+            else:
+                raise FloatingPointError("non-finite loss or gradient even with the reverse pass scaled by 2^-24")
+            if nfev < maxfun:
+                continue
+        break
+    return LbfgsResult(fun=rec["f"], nit=nit, nfev=nfev, status=rec["status"], message=_LBFGS_MESSAGES.get(rec["status"], "?"),
+                       success=rec["status"] in (1, 2), max_abs_grad=rec["max_abs_grad"], pairs=rec["pairs"], skipped=rec["skipped"])
+
+
 class DeepHPM(NetApi):
     """Drop-in for the reference's model class on the wave cases (INF:21-376)."""
 
@@ -498,6 +579,16 @@ class DeepHPM(NetApi):
                        + lay["SRC"] * out["loss_SRC"] + lay["NB"] * out["loss_NB"] + lay["FIX"] * out["loss_FIX"])
         return out
 
+    def _loss_coeffs(self, n_blk):
+        """_terms_from_sums(...)["loss"] as a coefficient vector over the sums buffer (8 floats per slot): the loss is linear in it"""
+        lay = self.layout
+        c = np.zeros((len(_SLOTS), 8))
+        c[0, :4], c[0, 4:7] = lay["f_uv"] / n_blk, lay["f_s"] / n_blk
+        for k, name in enumerate(_SLOTS[1:], start=1):
+            if name in self._sides:
+                c[k, list(self._sides[name][4])] = lay[name] / self._sides[name][5]
+        return c.reshape(-1).tolist()
+
     # ------------------------------------------------------------------------------------------
     # training drivers
     # ------------------------------------------------------------------------------------------
@@ -556,8 +647,9 @@ class DeepHPM(NetApi):
         """L-BFGS-B stage of INF:321-335: scipy on the host over a float64 copy of the flat
         parameter vector, loss and gradient from the device kernels; ``callback`` fires once per
         function evaluation like ScipyOptimizerInterface's loss_callback.  ``backend="torch"``: the same stage with the
-        optimizer on the device as well (lbfgs_on_device), for when the host update is the bottleneck."""
-        import scipy.optimize
+        optimizer on the device as well (lbfgs_on_device), for when the host update is the bottleneck.  ``backend="hip"``: the library's own
+        L-BFGS (lbfgs_hip): no host round trip per evaluation, the callbacks arrive in batches.  Any other name raises ValueError."""
+        check_backend(backend)
         P = self.n_params
         opts = dict(BFGS_OPTIONS[self.case])
         if options:
@@ -588,6 +680,11 @@ class DeepHPM(NetApi):
                     return tm["loss"], self._buf[:P]
                 result = lbfgs_on_device(self.theta, loss_and_grad, opts, self.callback)
                 continue
+            if backend == "hip":
+                result = lbfgs_hip(self.engine, self.theta, evaluate, P, self._loss_coeffs(idx_end - idx_start), opts, self.callback,
+                                   check=self._check_collective, shift_state=self._shift_state)
+                continue
+            import scipy.optimize
             x0 = self.theta.detach().cpu().numpy().astype(np.float64)
             result = scipy.optimize.minimize(fun, x0, jac=True, method='L-BFGS-B', options=opts)
             self.theta.copy_(torch.from_numpy(result.x.astype(np.float32)).to(self.device))

@@ -16,7 +16,47 @@ def param_count(layers: Sequence[int]) -> int:
     return sum(layers[i] * layers[i + 1] + layers[i + 1] for i in range(len(layers) - 1))
 
 
-class HipEngine:
+class LbfgsState:
+    """The caller-owned state buffer of pinn_lbfgs_* (include/pinn_hip.h): a byte tensor and its 256-byte aligned window"""
+
+    def __init__(self, lib, device, n_params: int, history: int):
+        self.n_params, self.history = int(n_params), int(history)
+        self.nbytes = lib.lbfgs_state_bytes(n_params, history)
+        if self.nbytes == 0:
+            raise PinnLibError(f"no L-BFGS state for n_params={n_params}, history={history} (history must be 1..64)")
+        self.buf = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=device)
+        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+
+
+class LbfgsMixin:
+    """pinn_lbfgs_* on tensors of ``self.device`` through ``self.lib`` (a capi.PinnLib), enqueued on ``self._stream()``.  HipEngine is the product's
+    user; the only synchronising methods are lbfgs_status / lbfgs_losses / lbfgs_debug."""
+
+    def lbfgs_state(self, n_params: int, history: int) -> LbfgsState:
+        return LbfgsState(self.lib, self.device, n_params, history)
+
+    def lbfgs_init(self, state: LbfgsState, options: dict, loss_coeffs, grad_scale: float = 1.0):
+        """options: scipy's names (maxcor = state.history, maxiter, maxfun, maxls, ftol, gtol); loss = sum_j loss_coeffs[j] * sums[j]"""
+        self.lib.lbfgs_init(state.ptr, state.nbytes, state.n_params, dict(options, maxcor=state.history), loss_coeffs, grad_scale, self._stream())
+
+    def lbfgs_advance(self, state: LbfgsState, params: torch.Tensor, grad: torch.Tensor, sums: torch.Tensor):
+        """Consumes the evaluation at ``params`` (grad, sums) and writes the next point to evaluate into ``params``.  Asynchronous."""
+        for a in (params, grad):
+            assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == state.n_params and a.device.type == self.device.type
+        assert sums.dtype == torch.float32 and sums.is_contiguous()
+        self.lib.lbfgs_advance(state.ptr, params.data_ptr(), grad.data_ptr(), sums.data_ptr(), self._stream())
+
+    def lbfgs_status(self, state: LbfgsState) -> dict:
+        return self.lib.lbfgs_status(state.ptr, self._stream())
+
+    def lbfgs_losses(self, state: LbfgsState, first: int, count: int):
+        return self.lib.lbfgs_read_losses(state.ptr, first, count, self._stream())
+
+    def lbfgs_debug(self, state: LbfgsState):
+        return self.lib.lbfgs_debug_read(state.ptr, state.n_params, state.history, self._stream())
+
+
+class HipEngine(LbfgsMixin):
     """loss/gradient, fields and Adam on one GPU, on flat fp32 parameter vectors.
 
     All tensors are fp32 CUDA(HIP) tensors; points are SoA (x, y, t).  Methods enqueue on the

@@ -17,7 +17,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .elastic_wave import _col, all_reduce_sum, evaluate_with_finite_gradient, pack_params, unpack_params, xavier_init  # noqa: F401
+from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, unpack_params, xavier_init  # noqa: F401
 from .net_api import NetApi, read_checkpoint, write_checkpoint
 
 OUT = ("u", "v", "w", "ut", "vt", "wt", "s11", "s22", "s33", "s12", "s13", "s23")
@@ -293,9 +293,21 @@ class NavierCauchy3D(NetApi):
                     lst.append(tm[key])
         return hist
 
-    def train_bfgs(self, batch_num, options: Optional[dict] = None):
-        """host L-BFGS-B stage (scipy, float64 flat vector) on the device kernels, as SEMI:330-344"""
-        import scipy.optimize
+    def _loss_coeffs(self, n_blk):
+        """_terms_from_sums(...)["loss"] as a coefficient vector over the sums buffer (16 floats per slot)"""
+        lay = self.layout
+        c = np.zeros((len(_SLOTS), 16))
+        c[0, :6], c[0, 6:12] = lay["f_uv"] / n_blk, lay["f_s"] / n_blk
+        for k, name in enumerate(_SLOTS[1:], start=1):
+            if name in self._sides and name in lay:
+                c[k, list(self._sides[name][5])] = lay[name] / self._sides[name][6]
+        return c.reshape(-1).tolist()
+
+    def train_bfgs(self, batch_num, options: Optional[dict] = None, backend: str = "scipy"):
+        """L-BFGS stage on the device kernels, as SEMI:330-344.  ``backend="scipy"`` (default): scipy's L-BFGS-B on the host over a float64
+        copy of the flat vector; ``"torch"``: torch.optim.LBFGS on the device (elastic_wave.lbfgs_on_device); ``"hip"``: the library's own
+        L-BFGS, no host round trip per evaluation (elastic_wave.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError."""
+        check_backend(backend)
         P, L = self.n_params, len(_SLOTS)
         opts = dict(maxiter=1000, maxfun=1000, maxcor=50, maxls=50, ftol=0.001 * float(np.finfo(float).eps))       # SEMI:130-137
         if options:
@@ -315,6 +327,17 @@ class NavierCauchy3D(NetApi):
                 self.callback(tm["loss"])
                 return tm["loss"], host[:P].astype(np.float64)
 
+            if backend == "torch":
+                def loss_and_grad():
+                    host = evaluate_with_finite_gradient(self.engine, evaluate, 0, self._shift_state, device_check=P, check=self._check_collective)
+                    return self._terms_from_sums(host.reshape(L, 16), hi - lo)["loss"], self._buf[:P]
+                result = lbfgs_on_device(self.theta, loss_and_grad, opts, self.callback)
+                continue
+            if backend == "hip":
+                result = lbfgs_hip(self.engine, self.theta, evaluate, P, self._loss_coeffs(hi - lo), opts, self.callback,
+                                   check=self._check_collective, shift_state=self._shift_state)
+                continue
+            import scipy.optimize
             result = scipy.optimize.minimize(fun, self.theta.detach().cpu().numpy().astype(np.float64), jac=True, method='L-BFGS-B', options=opts)
             self.theta.copy_(torch.from_numpy(result.x.astype(np.float32)).to(self.device))
         return result

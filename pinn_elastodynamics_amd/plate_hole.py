@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .elastic_wave import _col, all_reduce_sum, evaluate_with_finite_gradient, lbfgs_on_device, pack_params, relax_adjoint_shift, unpack_params, xavier_init  # noqa: F401
+from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, relax_adjoint_shift, unpack_params, xavier_init  # noqa: F401
 from .net_api import NetApi, read_checkpoint, write_checkpoint
 
 _EPS = float(np.finfo(float).eps)
@@ -326,7 +326,9 @@ class PINN(NetApi):
         return res
 
     def train_bfgs(self, options: Optional[dict] = None, backend: str = "scipy"):          # PLATE:508-526
-        """backend="torch": the optimizer runs on the device too (elastic_wave.lbfgs_on_device)."""
+        """backend="torch": the optimizer runs on the device too (elastic_wave.lbfgs_on_device); backend="hip": the library's own L-BFGS, no host
+        round trip per evaluation (elastic_wave.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError."""
+        check_backend(backend)
         P = self.theta["uv"].numel()
 
         def evaluate():
@@ -349,6 +351,11 @@ class PINN(NetApi):
                 relax_adjoint_shift(self.eng["uv"], loss, self._shift_state)
                 return loss, self._buf[:P]
             return lbfgs_on_device(self.theta["uv"], loss_and_grad, opts, self.callback)
+        if backend == "hip":
+            c = np.zeros(16)                             # _terms(...)["loss"] as coefficients of the 16 sums
+            c[0:5], c[8:10] = 10.0 / self.n_collo, 10.0 / self.n_hole
+            return lbfgs_hip(self.eng["uv"], self.theta["uv"], evaluate, P, c.tolist(), opts, self.callback, check=self._check_collective,
+                             shift_state=self._shift_state)
         return self._bfgs("uv", fun, opts)
 
     def _pretrain_loss_grad(self, key, sets):
@@ -376,7 +383,62 @@ class PINN(NetApi):
             total = total + ls.sum() * float(w.max() / n)           # kernel sums are normalised by max|w|
         return float(total.item()), grad.detach().cpu().numpy().astype(np.float64)
 
-    def _pretrain(self, key, sets, cb, options):
+    def _pretrain_coeffs(self, key, sets):
+        """c with  loss = sum_j c[j] * buf[P + j]  for the buffer _pretrain_enqueue fills (8 sums per set): the library normalises the sums it
+        reports by the largest weight -- of the whole call where all sets go in one call, of each set otherwise.  No launch."""
+        eng = self.eng[key]
+        nout = int(eng.layers[-1])
+        c = np.zeros((len(sets), 8))
+        per_set = [float(np.abs(w).max() / n) for _, _, w, n in sets]
+        for k in range(len(sets)):
+            c[k, :nout] = max(per_set) if hasattr(eng, "stream_loss_grad_multi") else per_set[k]
+        return c.reshape(-1)
+
+    def _pretrain_enqueue(self, key, sets):
+        """The pre-training loss and gradient left on the device in buf = [grad | 8 sums per set] (loss = _pretrain_coeffs . sums); nothing
+        synchronises.  One library call for all sets where the engine has it."""
+        eng, th = self.eng[key], self.theta[key]
+        P, m = th.numel(), len(sets)
+        buf = self.__dict__.setdefault("_pre_buf", {}).get(key)
+        if buf is None or buf.numel() != P + 8 * m:
+            buf = self._pre_buf[key] = torch.zeros(P + 8 * m, dtype=torch.float32, device=self.device)
+        if hasattr(eng, "stream_loss_grad_multi"):
+            rows = [(x, y, t, tg, (w / n).tolist(), buf[P + 8 * k:P + 8 * k + 8]) for k, ((x, y, t), tg, w, n) in enumerate(sets)]
+            eng.stream_loss_grad_multi(th, rows, self.lb, self.ub, False, grad_out=buf[:P], accumulate=False)
+        else:
+            for k, ((x, y, t), tg, w, n) in enumerate(sets):
+                eng.stream_loss_grad(th, x, y, t, self.lb, self.ub, False, tg, (w / n).tolist(), grad_out=buf[:P], accumulate=k > 0,
+                                     loss_out=buf[P + 8 * k:P + 8 * k + 8])
+        return buf
+
+    def _pretrain(self, key, sets, cb, options, backend="scipy"):
+        check_backend(backend)
+        if backend != "scipy":
+            eng, th = self.eng[key], self.theta[key]
+            P = th.numel()
+            opts = dict(BFGS_OPTIONS[key], **(options or {}))
+            c = self._pretrain_coeffs(key, sets)
+
+            def evaluate():
+                return self._pretrain_enqueue(key, sets)
+
+            if backend == "hip":
+                # ScipyOptimizerInterface(1000 * loss_X, ...) PLATE:220,230: the factor goes into the coefficients and the gradient scale;
+                # the callbacks see the unscaled loss (PLATE:527-559).  The stream losses have no adjoint-shift retry: no ladder.
+                res = lbfgs_hip(eng, th, evaluate, P, (1000.0 * c).tolist(), opts, cb, grad_scale=1000.0, loss_scale=1000.0,
+                                check=self._check_collective, ladder=False, what=f"pre-training of the {key!r} net")
+            else:
+                def loss_and_grad():
+                    buf = evaluate()
+                    loss = float(c @ buf[P:].detach().cpu().numpy().astype(np.float64))
+                    if not (np.isfinite(loss) and bool(torch.isfinite(buf[:P]).all())):
+                        raise FloatingPointError(f"pre-training of the {key!r} net produced a non-finite loss or gradient "
+                                                 f"(loss = {loss}); restart from other weights or use precision='bf16x3'")
+                    return 1000.0 * loss, 1000.0 * buf[:P]
+                res = lbfgs_on_device(th, loss_and_grad, opts, lambda f: cb(f / 1000.0))
+            self.refresh_frozen()
+            return res
+
         def fun(th):
             self.theta[key].copy_(torch.from_numpy(th.astype(np.float32)).to(self.device))
             loss, g = self._pretrain_loss_grad(key, sets)
@@ -391,11 +453,12 @@ class PINN(NetApi):
         self.refresh_frozen()
         return res
 
-    def train_bfgs_dist(self, options: Optional[dict] = None):     # PLATE:527-544
-        return self._pretrain("dist", self._dist_sets, self.callback_dist, options)
+    def train_bfgs_dist(self, options: Optional[dict] = None, backend: str = "scipy"):     # PLATE:527-544
+        """backend: "scipy" (default), "torch" or "hip" as in train_bfgs; with "hip" the gradient never leaves the device"""
+        return self._pretrain("dist", self._dist_sets, self.callback_dist, options, backend)
 
-    def train_bfgs_part(self, options: Optional[dict] = None):     # PLATE:546-559
-        return self._pretrain("part", self._part_sets, self.callback_part, options)
+    def train_bfgs_part(self, options: Optional[dict] = None, backend: str = "scipy"):     # PLATE:546-559
+        return self._pretrain("part", self._part_sets, self.callback_part, options, backend)
 
     # ---- inference / diagnostics ----------------------------------------------------------------------------------------
     def predict(self, x_star, y_star, t_star):       # PLATE:561-570

@@ -1,0 +1,57 @@
+"""CPU stand-in engine for the backend="hip" host tests: tests/_oracle_engine.OracleEngine (float64 numpy losses and gradients on CPU tensors)
+plus the lbfgs_* methods of the product's engine, run through the x86 emulator build of the library (build/emu/libpinn_emu.so) on the same
+CPU tensors.  Tests only."""
+import os
+import subprocess
+
+import torch
+
+from pinn_elastodynamics_amd.capi import PinnLib
+from pinn_elastodynamics_amd.hip_engine import LbfgsMixin
+from tests._oracle_engine import OracleEngine
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_LIB = None
+
+
+def emu_lib():
+    global _LIB
+    if _LIB is None:
+        subprocess.run(["make", "-C", os.path.join(ROOT, "pinn_elastodynamics_amd", "csrc"), "-j", str(min(16, os.cpu_count() or 1)), "emu"],
+                       check=True, stdout=subprocess.DEVNULL)
+        _LIB = PinnLib(os.path.join(ROOT, "build", "emu", "libpinn_emu.so"))
+    return _LIB
+
+
+class LbfgsOracleEngine(LbfgsMixin, OracleEngine):
+    def __init__(self, layers):
+        OracleEngine.__init__(self, layers)
+        self.lib = emu_lib()
+        self.advances = 0
+
+    def for_layers(self, layers):
+        return LbfgsOracleEngine(layers)
+
+    def _stream(self):
+        return 0
+
+    def lbfgs_advance(self, state, params, grad, sums):
+        self.advances += 1
+        return LbfgsMixin.lbfgs_advance(self, state, params, grad, sums)
+
+
+class OverflowingEngine(LbfgsOracleEngine):
+    """The 16-bit reverse pass overflowing: from the `nan_from`-th wave evaluation on, the gradient comes back NaN (the sums stay right) until
+    adjoint_shift has been raised"""
+
+    def __init__(self, layers, nan_from):
+        super().__init__(layers)
+        self.nan_from, self.wave_calls, self.poisoned = nan_from, 0, 0
+
+    def wave_loss_grad(self, *a, **kw):
+        out = super().wave_loss_grad(*a, **kw)
+        self.wave_calls += 1
+        if self.adjoint_shift < 4 and self.wave_calls > self.nan_from:
+            kw["grad_out"].fill_(float("nan"))
+            self.poisoned += 1
+        return out
