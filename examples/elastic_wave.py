@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--save", default="uv_NN.npz")
     ap.add_argument("--fem", default="", help="FEM ProbeData-<i>.mat file pattern with {i}, compared at the predicted frames")
     ap.add_argument("--precision", default="f16x3")
+    ap.add_argument("--refine-every", type=int, default=0, help="residual-adaptive refinement of the collocation set every N Adam steps (0 = off)")
+    ap.add_argument("--refine-frac", type=float, default=0.05, help="fraction of the collocation rows offered for replacement at each refinement")
     a = ap.parse_args()
 
     if "RANK" in os.environ:
@@ -53,7 +55,29 @@ def main():
         model = DeepHPMConfined(c["Collo"], c["SRC"], c["IC"], c["FIXED"], None, c["uv_layers"], None, None, c["lb"], c["ub"], uvDir=a.load,
                                 precision=a.precision, verbose=rank == 0)
     t0 = time.time()
-    if a.iters:
+    if a.iters and a.refine_every > 0:
+        # Adam in blocks of --refine-every steps; between blocks the lowest-scoring rows give way to higher-scoring fresh candidates
+        # (Latin hypercube in the box minus the source disc, like the set itself; every rank draws its own)
+        xc, yc, r = c["source"]
+        lbv, ubv = np.asarray(c["lb"], dtype=np.float64), np.asarray(c["ub"], dtype=np.float64)
+        n_rep = max(1, int(a.refine_frac * c["Collo"].shape[0]))
+        hist, done, rnd = None, 0, 0
+        while done < a.iters:
+            steps = min(a.refine_every, a.iters - done)
+            h = model.train(iter=steps, learning_rate=a.lr, batch_num=a.batch_num)
+            hist = h if hist is None else tuple(p + q for p, q in zip(hist, h))
+            done += steps
+            if done < a.iters:
+                rnd += 1
+                cand = lbv + (ubv - lbv) * ps.lhs(3, 4 * n_rep, rng=7919 * rnd + rank)
+                cand = cand[(cand[:, 0] - xc) ** 2 + (cand[:, 1] - yc) ** 2 > r * r]
+                info = model.refine_collocation(cand, n_rep)
+                if rank == 0:
+                    print("refinement %d: %d rows replaced (largest score out %s, smallest in %s)"
+                          % (rnd, info["replaced"], info["score_replaced_max"], info["score_inserted_min"]))
+        if rank == 0:
+            print("Adam: loss %.4e -> %.4e" % (hist[-1][0], hist[-1][-1]))
+    elif a.iters:
         hist = model.train(iter=a.iters, learning_rate=a.lr, batch_num=a.batch_num)
         if rank == 0:
             print("Adam: loss %.4e -> %.4e" % (hist[-1][0], hist[-1][-1]))

@@ -83,7 +83,7 @@ enum {
     PINN_ERR_LAYERS = -2,      /* unsupported layer list (see pinn_supported_width) */
     PINN_ERR_PRECISION = -3,   /* unknown precision_mode */
     PINN_ERR_WORKSPACE = -4,   /* workspace smaller than pinn_min_workspace_bytes() or misaligned */
-    PINN_ERR_SIZE = -5,        /* n < 0 (n == 0 is a valid empty batch: zero sums, zero / untouched gradient) */
+    PINN_ERR_SIZE = -5,        /* n < 0 (n == 0 is a valid empty batch: zero sums, zero / untouched gradient); pinn_select_k: n >= 2^31 or k outside 0 .. n */
     PINN_ERR_COLLECTIVE = -6,  /* pinn_p2p_*: not connected; a coarse-grained buffer across devices (pinn_p2p_connect); or a rank did not arrive within the
                                 * bounded wait of some call (pinn_p2p_set_timeout_ms, default 30 s) -- that call's buffer is then NaN on this rank */
     PINN_ERR_RANGE = -7,       /* pinn_wave2d_loss_grad_checked: gradient non-finite even on the two-kernel path with the reverse pass scaled by 2^-24 */
@@ -175,6 +175,37 @@ int pinn_wave2d_fields(const float* params_flat, const int* layers, int n_layers
                        const float* x, const float* y, const float* t, int64_t n,
                        const double lb[3], const double ub[3], int normalize,
                        float* fields_out, int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* Per-point residual measure of the wave family -- net_f_sig (INF:221-265) evaluated for ranking, not for a loss:
+ *   score_out[n] = sum_i term_weights[i] * f_i(n)^2,  i in (f_u,f_v,f_ut,f_vt,f_s11,f_s22,f_s12)   (INF:265 order)
+ * score_out is a DEVICE array of n floats, term_weights a host array used as given (no normalisation).  Forward only: the four streams of
+ * pinn_wave2d_fields, the seven residuals formed from them in the kernel, one float stored per point (fields stores 28).  Every compiled
+ * family (all widths and operand modes, any depth) and PINN_PREC_FP32; one launch behind the repack, so pinn_min_workspace_bytes() is
+ * enough for any n (PINN_PREC_FP32 walks the points in passes, as its fields call does); honours PINN_FLAG_WEIGHTS_PACKED; n == 0 is a
+ * valid no-op.  Not a loss + gradient call: pinn_debug_path_counts does not count it.
+ * Accuracy: the forward is the one of pinn_wave2d_fields in the same mode (the same kernel code up to the head); on top of it the head rounds
+ * at most 16 eps32 * sum_i w_i a_i^2, a_i = the sum of the absolute values of the terms of f_i (measured: <= 0.12 of that bound in every
+ * family).  Against the float64 residuals, relative L2 of s and of sqrt(s) over 1000 collocation points as a multiple of the same error of the
+ * residuals evaluated in float32 on the host (MI355X; profiles/residual_score_accuracy.txt): f16x3 1.4 / 1.2 / 1.2 at fresh 4x32, fresh 8x64 and
+ * the reference's trained 8x80 net, PINN_PREC_FP32 1.1 / 1.8 / 1.0.  Inside the source disc, where a trained net was never asked to satisfy the
+ * equations, single points reach scores 1e6 times the median; a norm over a set that contains one is that point's rounding alone. */
+int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int n_layers,
+                               const float* x, const float* y, const float* t, int64_t n,
+                               const double lb[3], const double ub[3], int normalize,
+                               double E, double mu, double rho, int plane_strain,
+                               const float term_weights[7], float* score_out,
+                               int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* Deterministic top-k / bottom-k selection on the device: which k of the n floats in `score` are the largest (largest != 0) or the smallest.
+ *   order   each float maps to a uint32 key that is monotone in the float order (sign-flip map: -0 < +0, a positive NaN above +inf, a negative
+ *           NaN below -inf); elements are ordered by key (descending if `largest`, else ascending), then by index ascending
+ *   result  the first k indices of that order, written to idx_out (device int32[k]) in ASCENDING INDEX order
+ * Radix select on the keys (four 8-bit passes), then a stable compaction; integer atomics only, so the result is exactly reproducible; no host
+ * synchronisation; any n.  `workspace` is device memory of pinn_select_workspace_bytes(n) bytes, 256-byte aligned, scratch of the call.
+ * k == 0 is a valid no-op.  Errors: n < 0, n >= 2^31 or k outside 0 .. n: PINN_ERR_SIZE; short or misaligned workspace: PINN_ERR_WORKSPACE. */
+size_t pinn_select_workspace_bytes(int64_t n);
+int pinn_select_k(const float* score, int64_t n, int64_t k, int largest, int32_t* idx_out,
+                  void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- plate-with-hole family (PLATE = PlateHoleQuarter/train/train.py); precision_mode must be a split mode ---------------
  * Streams of one net at raw or normalised (x,y,t): streams_out is SoA [5][n_out][n] = Y, dY/dx, dY/dy, dY/dt, d2Y/dt2.

@@ -135,6 +135,12 @@ class PinnLib:
         L.pinn_wave2d_fields.restype = i32
         L.pinn_net_streams.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, i32, vp, sz, vp]
         L.pinn_net_streams.restype = i32
+        L.pinn_wave2d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, i32, pf32, vp, i32, vp, sz, vp]
+        L.pinn_wave2d_residual_score.restype = i32
+        L.pinn_select_workspace_bytes.argtypes = [i64]
+        L.pinn_select_workspace_bytes.restype = sz
+        L.pinn_select_k.argtypes = [vp, i64, i64, i32, vp, vp, sz, vp]
+        L.pinn_select_k.restype = i32
         L.pinn_plate2d_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, vp, i32, i32, vp, sz, vp]
         L.pinn_plate2d_loss_grad.restype = i32
         L.pinn_plate2d_traction_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
@@ -391,6 +397,20 @@ class PinnLib:
         rc = self.lib.pinn_wave2d_fields(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
                                          int(bool(normalize)), fields_out, mode_bits(prec), ws, int(ws_bytes), stream)
         self.check(rc, "pinn_wave2d_fields")
+
+    def wave2d_residual_score(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, score_out, prec, ws,
+                              ws_bytes, stream=0):
+        rc = self.lib.pinn_wave2d_residual_score(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
+                                                 int(bool(normalize)), float(E), float(mu), float(rho), int(bool(plane_strain)),
+                                                 self._floats(term_weights, 7), score_out, mode_bits(prec), ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_wave2d_residual_score")
+
+    def select_workspace_bytes(self, n) -> int:
+        return int(self.lib.pinn_select_workspace_bytes(int(n)))
+
+    def select_k(self, score, n, k, largest, idx_out, ws, ws_bytes, stream=0):
+        rc = self.lib.pinn_select_k(score, int(n), int(k), int(bool(largest)), idx_out, ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_select_k")
 
     def net_streams(self, params, layers, x, y, t, n, lb, ub, normalize, streams_out, prec, ws, ws_bytes, stream=0):
         rc = self.lib.pinn_net_streams(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),

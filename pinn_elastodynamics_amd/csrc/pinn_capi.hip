@@ -3,6 +3,7 @@
 #include "pinn_host.hpp"
 #include "pinn_fp32.hpp"
 #include "pinn_lbfgs.hpp"
+#include "pinn_select.hpp"
 
 #ifndef PINN_VARIANTS_DEF
 #define PINN_VARIANTS_DEF "pinn_variants.def"     // experiments (tools/exp_build.sh) build a one-variant library
@@ -228,7 +229,7 @@ const char* pinn_error_string(int code) {
         case PINN_ERR_LAYERS: return "unsupported layer list (need {3, H x k, n_out<=8} -- {4, H x k, 12} for the 3-D entry points --, H<=160, <=16 weight layers, and a compiled variant)";
         case PINN_ERR_PRECISION: return "unknown precision_mode";
         case PINN_ERR_WORKSPACE: return "workspace too small or not 256-byte aligned";
-        case PINN_ERR_SIZE: return "n must not be negative";
+        case PINN_ERR_SIZE: return "n must not be negative (pinn_select_k: n < 2^31 and 0 <= k <= n)";
         case PINN_ERR_COLLECTIVE: return "p2p collective: not connected, a coarse-grained buffer across devices, or a rank did not arrive within the bounded wait (the call failed as a whole: buffer NaN, no Adam update)";
         case PINN_ERR_STATE: return "L-BFGS state buffer too small, not 256-byte aligned, or not initialised for these sizes (pinn_lbfgs_state_bytes)";
         case PINN_ERR_HISTORY: return "L-BFGS history must be 1..64 pairs";
@@ -336,11 +337,11 @@ size_t pinn_min_workspace_bytes(const int* layers, int n_layers, int precision_m
 
 // PINN_PREC_FP32: plain fp32 arithmetic (pinn_fp32.hpp), the points walked in as many passes as the workspace holds.
 // ns = streams of the head (1: data / traction heads, 4: wave / fields, 5: plate family and the 4-input heads), din = inputs.
-static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3) {
+static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, bool counted = true) {
     hipStream_t st = c.stream;
     const size_t per_point = fp32_bytes_per_point(c.net, ns);
     if (((uintptr_t)c.ws & 255) != 0 || c.ws_bytes < per_point * 256) return PINN_ERR_WORKSPACE;
-    ++g_path_counts[PINN_PATH_FP32];
+    if (counted) ++g_path_counts[PINN_PATH_FP32];      // (the residual score is no loss + gradient call: not counted)
     long mmax = (long)(c.ws_bytes / per_point);
     if (mmax > (1L << 20)) mmax = 1L << 20;
     Fp32Args a;
@@ -372,7 +373,7 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3) {
     a.head = head;
     a.din = din;
     a.second = (din == 3 && ns == 5) ? 1 : 0;
-    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D;
+    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head == HEAD_SCORE;
     int pass = 0;
     for (long p0 = 0; p0 < c.n; p0 += mmax, ++pass) {
         a.p0 = p0;
@@ -615,6 +616,34 @@ int pinn_wave2d_fields(const float* params_flat, const int* layers, int n_layers
     if (n == 0) return 0;
     if (!impl) return fp32_call(c, HEAD_FIELDS, 0, 4);
     return impl->fields(c);
+}
+
+int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
+                               int64_t n, const double lb[3], const double ub[3], int normalize, double E, double mu, double rho,
+                               int plane_strain, const float term_weights[7], float* score_out, int precision_mode, void* workspace,
+                               size_t ws_bytes, void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (!term_weights || (n > 0 && !score_out)) return PINN_ERR_NULL;
+    if (c.net.nout != 7) return PINN_ERR_LAYERS;
+    set_hooke(c, E, mu, rho, plane_strain);
+    for (int i = 0; i < 7; ++i) c.tw[i] = term_weights[i];
+    c.fields_out = score_out;
+    if (n == 0) return PINN_OK;
+    if (!impl) return fp32_call(c, HEAD_SCORE, 0, 4, 3, false);
+    return impl->wave_score(c);
+}
+
+size_t pinn_select_workspace_bytes(int64_t n) { return (n < 0 || n >= (int64_t)1 << 31) ? 0 : select::WS_BYTES; }
+
+int pinn_select_k(const float* score, int64_t n, int64_t k, int largest, int32_t* idx_out, void* workspace, size_t ws_bytes, void* stream) {
+    if (n < 0 || n >= (int64_t)1 << 31 || k < 0 || k > n) return PINN_ERR_SIZE;
+    if (!workspace || (n > 0 && !score) || (k > 0 && !idx_out)) return PINN_ERR_NULL;
+    if (((uintptr_t)workspace & 255) != 0 || ws_bytes < select::WS_BYTES) return PINN_ERR_WORKSPACE;
+    if (k == 0) return PINN_OK;
+    return select::launch(score, (uint32_t)n, (uint32_t)k, largest != 0, idx_out, workspace, static_cast<hipStream_t>(stream));
 }
 
 int pinn_net_streams(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,

@@ -236,8 +236,10 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 // HEAD_NC3D   : 5 first-order streams (value, x, y, z, t), 4 inputs, 12 outputs: 3-D Navier-Cauchy residuals (build-side extension of
 //               INF:221-265, stated in oracle/nc3d_oracle.py; BASELINE.json configs[4])
 // HEAD_DATA3D : HEAD_DATA for the 4-input net (up to 16 outputs);  HEAD_FIELDS3D : HEAD_FIELDS for it (5 streams)
+// HEAD_SCORE  : forward only, 4 streams: one float per point, sum_i tw[i] f_i^2 of the wave residuals (pinn_wave2d_residual_score); written
+//               through `fields_out` as [n].  A score for another family is one more branch of the score block in Chain::run.
 enum { HEAD_WAVE = 0, HEAD_DATA = 1, HEAD_FIELDS = 2, HEAD_PLATE = 3, HEAD_TRACTION = 4, HEAD_STREAMS = 5, HEAD_NC3D = 6, HEAD_DATA3D = 7,
-       HEAD_FIELDS3D = 8 };
+       HEAD_FIELDS3D = 8, HEAD_SCORE = 9 };
 __host__ __device__ constexpr bool head_is_3d(int head) { return head == HEAD_NC3D || head == HEAD_DATA3D || head == HEAD_FIELDS3D; }
 constexpr int LOSS_SLOTS_3D = 16;     // per-wave loss partials: 8 slots for the reference's heads, 16 for the 3-D ones
 
@@ -253,14 +255,14 @@ struct ChainArgs {
     long ntiles;               // tiles in this chunk
     float sx[4], ox[4];        // input map x' = x*sx + ox  (INF:191 when normalising, identity otherwise); 4-input heads: index 2 = z, 3 = t
     float c1, c2, G, rho;      // Hooke coefficients (INF:238-241 / PLATE:416-418) and density
-    float tw[16];              // per-residual (HEAD_WAVE / HEAD_NC3D) or per-output (HEAD_DATA) weights, max-normalised
+    float tw[16];              // per-residual (HEAD_WAVE / HEAD_NC3D) or per-output (HEAD_DATA) weights, max-normalised (HEAD_SCORE: as given)
     const float* targets;      // HEAD_DATA: [nout][n] SoA targets or nullptr (= 0)
     uint16_t* S;               // forward-state panels of this chunk
     uint16_t* Z;               // adjoint panels of this chunk
     long S_tile_stride;        // in 16-bit elements
     long Z_tile_stride;
     float* loss_part;          // [total waves][8 or LOSS_SLOTS_3D] per-wave partial sums of squares
-    float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2])
+    float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  HEAD_SCORE: [n]
     const float* aux;          // HEAD_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
     float w5[5][8];            // HEAD_STREAMS: per (stream, output) weights, max-normalised
 };
@@ -696,7 +698,7 @@ struct Chain {
         const int wpb = blockDim.x >> 6;
         const long gwave = (long)blockIdx.x * wpb + (threadIdx.x >> 6), nwaves = (long)gridDim.x * wpb;
         const int nl = a.net.nl;
-        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D;
+        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || HEAD == HEAD_SCORE;
         constexpr bool SPILL = !FWD_ONLY;
         __shared__ __attribute__((aligned(16))) char spill_lds[4 * 1024];      // one 1 KB transpose record per wave (256-thread blocks)
         char* rec = spill_lds + (threadIdx.x >> 6) * 1024;
@@ -1003,6 +1005,26 @@ struct Chain {
                         if (q == 0) lsum[o] += vm * d * d;
                         adj[0][nb][o] = 2.0f * a.tw[o] * d * vm;
                     }
+                } else if constexpr (HEAD == HEAD_SCORE) {
+                    // per-point residual measure sum_i tw[i] f_i^2 from the streams at hand.  The seven lines are HEAD_WAVE's (net_f_sig
+                    // INF:221-265), kept as a second copy so that the loss kernels' code does not move; nothing is differentiated here.
+                    const float(&V)[8] = Y[0][nb];
+                    const float(&X)[8] = Y[1][nb];
+                    const float(&Yy)[8] = Y[2][nb];
+                    const float(&T)[8] = Y[3][nb];
+                    const float e11 = X[0], e22 = Yy[1], e12 = Yy[0] + X[1];          // INF:216-218
+                    float f[7];
+                    f[0] = X[4] + Yy[6] - a.rho * T[2];                               // f_u   INF:262
+                    f[1] = Yy[5] + X[6] - a.rho * T[3];                               // f_v   INF:263
+                    f[2] = T[0] - V[2];                                               // f_ut  INF:248
+                    f[3] = T[1] - V[3];                                               // f_vt  INF:249
+                    f[4] = V[4] - (a.c1 * e11 + a.c2 * e22);                          // f_s11 INF:244
+                    f[5] = V[5] - (a.c2 * e11 + a.c1 * e22);                          // f_s22 INF:246
+                    f[6] = V[6] - a.G * e12;                                          // f_s12 INF:245
+                    float sc = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) sc += a.tw[i] * (f[i] * f[i]);
+                    if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
                 } else {
                     // predict (INF:337-347): write Y and its tangent streams, [NS*nout][n]
                     if (q == 0 && valid[nb]) {

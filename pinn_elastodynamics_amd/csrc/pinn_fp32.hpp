@@ -39,7 +39,7 @@ struct Fp32Args {
     float* S;                  // [nl+1][ns][hr][m]: S_0 = inputs and tangent seeds (first din rows), S_l = state behind hidden layer l
     float* Z;                  // [nl+1][ns][hr][m]: Z_l = adjoint of the pre-activations of weight layer l (Z_nl: nout rows)
     float* fsq;                // [FP32_TERMS][m]: squared residuals of the pass
-    float* fields_out;         // fields heads: [ns][nout][n]
+    float* fields_out;         // fields heads: [ns][nout][n];  HEAD_SCORE: [n]
     int ns;                    // streams: 1, 4 (value, x, y, t) or 5 (+ tt for din = 3; value, x, y, z, t for din = 4)
     int hr;                    // row stride of S / Z: max(h, 16)
     int head;                  // HEAD_*
@@ -105,6 +105,22 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
         if (a.head == HEAD_FIELDS || a.head == HEAD_FIELDS3D) {
             for (int s = 0; s < ns; ++s)
                 for (int o = 0; o < NO; ++o) a.fields_out[((long)s * NO + o) * a.n + gp] = Y[s][o];
+            continue;
+        }
+        if (a.head == HEAD_SCORE) {
+            // pinn_wave2d_residual_score: sum_i tw[i] f_i^2 of the wave residuals (the lines of HEAD_WAVE below), one float per point through fields_out
+            const float e11 = Y[1][0], e22 = Y[2][1], e12 = Y[2][0] + Y[1][1];
+            float f[7];
+            f[0] = Y[1][4] + Y[2][6] - a.rho * Y[3][2];
+            f[1] = Y[2][5] + Y[1][6] - a.rho * Y[3][3];
+            f[2] = Y[3][0] - Y[0][2];
+            f[3] = Y[3][1] - Y[0][3];
+            f[4] = Y[0][4] - (a.c1 * e11 + a.c2 * e22);
+            f[5] = Y[0][5] - (a.c2 * e11 + a.c1 * e22);
+            f[6] = Y[0][6] - a.G * e12;
+            float sc = 0.0f;
+            for (int i = 0; i < 7; ++i) sc += a.tw[i] * (f[i] * f[i]);
+            a.fields_out[gp] = sc;
             continue;
         }
         // ---- head: residuals, their squares, adjoint seeds dL/dY

@@ -122,6 +122,8 @@ struct Impl {
     int (*nc3d_loss_grad)(const Call&);
     int (*nc3d_data_loss_grad)(const Call&);
     int (*nc3d_fields)(const Call&);
+    // per-point residual score of the wave family (forward only, HEAD_SCORE)
+    int (*wave_score)(const Call&);
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -811,6 +813,22 @@ struct Host {
         return (int)hipGetLastError();
     }
     static int fields(const Call& c) { return fields_ns<4, HEAD_FIELDS>(c); }
+    // pinn_wave2d_residual_score: the forward of `fields` with the score head (c.fields_out = float[n], c.tw as given); one launch, no panels,
+    // so the fixed part of the plan is all the workspace it needs; not a loss + gradient call: no path counter
+    static int wave_score(const Call& c) {
+        Plan p;
+        int rc = make_plan<4>(c, p, false);
+        if (rc) return rc;
+        rc = repack(c, p);
+        if (rc) return rc;
+        ChainArgs a;
+        fill_common(c, p, a);
+        for (int i = 0; i < 16; ++i) a.tw[i] = c.tw[i];
+        a.tile0 = 0;
+        a.ntiles = p.ntiles;
+        hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, nb<4>(), 4, HEAD_SCORE>), dim3(chain_blocks(p.ntiles)), dim3(256), 0, c.stream, a);
+        return (int)hipGetLastError();
+    }
 
     // 5-stream family (plate): split-precision variants only
     static int plate_loss_grad(const Call& c) {
@@ -1017,7 +1035,7 @@ struct Host {
     static const Impl* impl() {
         static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
                                &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
-                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields};
+                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score};
         return &I;
     }
 };

@@ -256,6 +256,38 @@ class HipEngine(LbfgsMixin):
                                out.data_ptr(), self.precision, self._ws_ptr, self.ws_bytes, self._stream())
         return out
 
+    # ---- residual-adaptive refinement: per-point score and selection ------------------------------------------------
+    def residual_score(self, params, x, y, t, lb, ub, normalize, term_weights, E=2.5, mu=0.25, rho=1.0, plane_strain=True,
+                       out: Optional[torch.Tensor] = None, packed: bool = False):
+        """Returns the device tensor [n] of  sum_i term_weights[i] * f_i(n)^2  (pinn_wave2d_residual_score): the wave residuals of
+        net_f_sig per point, formed in the kernel -- nothing but the score leaves it."""
+        n = x.numel()
+        for v in (x, y, t):
+            self._chk(v, n)
+        self._chk(params, self.n_params)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._chk(out, n)
+        self.lib.wave2d_residual_score(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, E, mu, rho,
+                                       plane_strain, term_weights, out.data_ptr(), PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0),
+                                       self._ws_ptr, self.ws_bytes, self._stream())
+        return out
+
+    def select_k(self, score, k: int, largest: bool = True):
+        """The k largest (or smallest) entries of the device tensor ``score`` as a device int32 [k] of ASCENDING indices (pinn_select_k):
+        ties go to the lowest index, a NaN ranks above +inf, the result is exactly reproducible.  No synchronisation."""
+        self._chk(score)
+        n = score.numel()
+        ws = self.__dict__.get("_select_ws")
+        if ws is None:                      # (the size does not depend on n: one buffer per engine)
+            nbytes = self.lib.select_workspace_bytes(0)
+            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            self._select_ws = ws
+            self._select_ws_ptr, self._select_ws_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
+        out = torch.empty(int(k), dtype=torch.int32, device=self.device)
+        self.lib.select_k(score.data_ptr(), n, k, largest, out.data_ptr(), self._select_ws_ptr, self._select_ws_bytes, self._stream())
+        return out
+
     # ---- plate family (5 streams: value, d/dx, d/dy, d/dt, d2/dt2) --------------------------------------------------
     def net_streams(self, params, x, y, t, lb, ub, normalize):
         """Returns [5, n_out, n]: the net's outputs, their first derivatives and the second time derivative."""
