@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--dist", default="")
     ap.add_argument("--uv", default="")
     ap.add_argument("--fem", default="", help="FEM ProbeData-<i>.mat pattern with {i}")
+    ap.add_argument("--refine-every", type=int, default=0, help="residual-adaptive refinement of the collocation set every N Adam steps (0 = off)")
+    ap.add_argument("--refine-frac", type=float, default=0.05, help="fraction of the collocation rows offered for replacement at each refinement")
     a = ap.parse_args()
 
     c = ps.plate_case(n_collo=a.n_collo, n_refine=a.n_refine)
@@ -39,7 +41,23 @@ def main():
         model.train_bfgs_part(options=dict(maxiter=a.pre_iters, maxfun=a.pre_iters))
         model.count = 0
     t0 = time.time()
-    if a.iters:
+    if a.iters and a.refine_every > 0:
+        # Adam in blocks of --refine-every steps; between blocks the lowest-scoring rows give way to higher-scoring fresh candidates from the
+        # case's own sampler (Latin hypercube in the plate, the hole removed); the frozen D / P streams of a replaced row follow it
+        n_rep = max(1, int(a.refine_frac * c["Collo"].shape[0]))
+        done, rnd = 0, 0
+        while done < a.iters:
+            steps = min(a.refine_every, a.iters - done)
+            model.train(iter=steps, learning_rate=a.lr)
+            done += steps
+            if done < a.iters:
+                rnd += 1
+                cand = ps.DelHolePT(c["lb"] + (c["ub"] - c["lb"]) * ps.lhs(3, 4 * n_rep, rng=7919 * rnd + model.rank))
+                info = model.refine_collocation(cand, n_rep)
+                if model.rank == 0:
+                    print("refinement %d: %d rows replaced (largest score out %s, smallest in %s)"
+                          % (rnd, info["replaced"], info["score_replaced_max"], info["score_inserted_min"]))
+    elif a.iters:
         model.train(iter=a.iters, learning_rate=a.lr)
     if a.bfgs_iters:
         model.train_bfgs(options=dict(maxiter=a.bfgs_iters, maxfun=a.bfgs_iters))

@@ -228,6 +228,30 @@ int pinn_plate2d_loss_grad(const float* params_flat, const int* layers, int n_la
                            float* loss_terms_out, float* grad_flat_out, int accumulate,
                            int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
+/* Per-point residual measure of the plate family -- net_f_sig of the plate (composite PLATE:358-388, residuals PLATE:404-439) evaluated for
+ * ranking, not for a loss:
+ *   score_out[n] = sum_i term_weights[i] * f_i(n)^2,  i in (f_u, f_v, f_s11, f_s22, f_s12)   (PLATE:439 order)
+ * score_out is a DEVICE array of n floats, term_weights a host array used as given (no normalisation), frozen_streams the [2][5][5][n] array
+ * of pinn_plate2d_loss_grad at the same points.  Forward only: the five streams of pinn_net_streams, the composite and the five residuals
+ * formed from them in the kernel, one float stored per point (pinn_net_streams stores 25 and leaves the composite to the caller).  Split
+ * modes of every compiled width and PINN_PREC_FP32 (the other 16-bit modes: PINN_ERR_PRECISION, as the loss call); one launch behind the
+ * repack, so pinn_min_workspace_bytes() is enough for any n (PINN_PREC_FP32 walks the points in passes); honours PINN_FLAG_WEIGHTS_PACKED;
+ * n == 0 is a valid no-op.  Not a loss + gradient call: pinn_debug_path_counts does not count it.
+ * Accuracy: the forward is the one of pinn_net_streams in the same mode (the same kernel code up to the head); on top of it the head rounds
+ * at most 24 eps32 * sum_i |w_i| a_i^2, a_i = the sum of the absolute values of the leaf terms (P, D*N, 2*D*N, with their coefficients) of f_i
+ * (measured: <= 0.10 of that bound in every family).  Against the float64 residuals, relative L2 of s and of sqrt(s) over 1000
+ * collocation points as a multiple of the same error of the residuals evaluated in float32 on the host (MI355X;
+ * profiles/residual_score_accuracy.txt), D and P from the reference's trained nets: f16x3 0.55 / 1.08 at a fresh 4x32 net,
+ * 1.16 / 1.74 at the reference's trained 8x70 net, 1.92 / 2.32 at the trained 8x64 net; PINN_PREC_FP32 1.91 / 1.18, 0.73 / 1.11, 1.12 / 1.34.
+ * Timing (MI355X, 8x64, 1 M points, profiles/refine_family_calls.txt): 1.24 ms against 1.47 ms for pinn_net_streams plus the composite and
+ * residual formulas in torch on the device. */
+int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int n_layers,
+                                const float* x, const float* y, const float* t, int64_t n,
+                                const double lb[3], const double ub[3], int normalize,
+                                const float* frozen_streams, double E, double mu, double rho,
+                                const float term_weights[5], float* score_out,
+                                int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
 /* Replaces net_t + loss_HOLE (PLATE:452-461,192-193) and its gradient w.r.t. the uv net.
  *   frozen_and_normals: SoA [12][n] = D values (5 fields), P values (5 fields), nx, ny at the hole points
  *   loss_terms_out = (sum tx^2, sum ty^2) */
@@ -412,6 +436,25 @@ int pinn_nc3d_fields(const float* params_flat, const int* layers, int n_layers,
                      const float* x, const float* y, const float* z, const float* t, int64_t n,
                      const double lb[4], const double ub[4], int normalize,
                      float* fields_out, int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* Per-point residual measure of the 3-D family -- the twelve residuals stated in oracle/nc3d_oracle.py (no reference lines: see above)
+ * evaluated for ranking:
+ *   score_out[n] = sum_i term_weights[i] * f_i(n)^2,  i in the residual order above
+ * Conventions of pinn_wave2d_residual_score: score_out a DEVICE array of n floats, term_weights a host array used as given; forward only, the
+ * five streams of pinn_nc3d_fields, the residuals formed in the kernel, one float stored per point (fields stores 60); split modes of every
+ * compiled width and PINN_PREC_FP32; pinn_min_workspace_bytes() is enough for any n; honours PINN_FLAG_WEIGHTS_PACKED; n == 0 is a valid
+ * no-op; no path counter moves.
+ * Accuracy: the forward is the one of pinn_nc3d_fields in the same mode; on top of it the head rounds at most 24 eps32 * sum_i |w_i| a_i^2,
+ * a_i = the sum of the absolute values of the terms of f_i with their coefficients (measured: <= 0.08 of that bound in every family).
+ * Against the float64 residuals, relative L2 of s and of sqrt(s) over 1000 points as a multiple of the same error of the residuals
+ * evaluated in float32 on the host (MI355X; profiles/residual_score_accuracy.txt): f16x3 1.20 / 1.23 at a fresh 3x32 net, 0.76 / 0.76 at a fresh 10x128
+ * net; PINN_PREC_FP32 1.54 / 1.54, 1.70 / 1.70.  Timing (MI355X, 10x128, 1 M points, profiles/refine_family_calls.txt): 4.49 ms against
+ * 4.85 ms for pinn_nc3d_fields plus the residual formulas in torch on the device. */
+int pinn_nc3d_residual_score(const float* params_flat, const int* layers, int n_layers,
+                             const float* x, const float* y, const float* z, const float* t, int64_t n,
+                             const double lb[4], const double ub[4], int normalize,
+                             double E, double mu, double rho, const float term_weights[12], float* score_out,
+                             int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
 /* Replaces tf.train.AdamOptimizer's update (INF:131-133; TF1 rule: epsilon outside the bias
  * correction).  step is 1-based.  All arrays are length n_params, updated in place. */

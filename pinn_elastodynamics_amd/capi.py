@@ -143,6 +143,10 @@ class PinnLib:
         L.pinn_select_k.restype = i32
         L.pinn_plate2d_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, vp, i32, i32, vp, sz, vp]
         L.pinn_plate2d_loss_grad.restype = i32
+        L.pinn_plate2d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, i32, vp, sz, vp]
+        L.pinn_plate2d_residual_score.restype = i32
+        L.pinn_nc3d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, pf32, vp, i32, vp, sz, vp]
+        L.pinn_nc3d_residual_score.restype = i32
         L.pinn_plate2d_traction_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
         L.pinn_plate2d_traction_loss_grad.restype = i32
         L.pinn_stream_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
@@ -424,6 +428,20 @@ class PinnLib:
                                              self._floats(term_weights, 5), loss_out, grad_out, int(bool(accumulate)), mode_bits(prec),
                                              ws, int(ws_bytes), stream)
         self.check(rc, "pinn_plate2d_loss_grad")
+
+    def plate2d_residual_score(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, E, mu, rho, term_weights, score_out, prec, ws, ws_bytes,
+                               stream=0):
+        rc = self.lib.pinn_plate2d_residual_score(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
+                                                  int(bool(normalize)), frozen, float(E), float(mu), float(rho), self._floats(term_weights, 5),
+                                                  score_out, mode_bits(prec), ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_plate2d_residual_score")
+
+    def nc3d_residual_score(self, params, layers, x, y, z, t, n, lb, ub, normalize, E, mu, rho, term_weights, score_out, prec, ws, ws_bytes,
+                            stream=0):
+        rc = self.lib.pinn_nc3d_residual_score(params, self._ints(layers), len(layers), x, y, z, t, int(n), self._d4(lb), self._d4(ub),
+                                               int(bool(normalize)), float(E), float(mu), float(rho), self._floats(term_weights, 12), score_out,
+                                               mode_bits(prec), ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_nc3d_residual_score")
 
     def plate2d_traction_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, aux, weights, loss_out, grad_out, accumulate,
                                    prec, ws, ws_bytes, stream=0):

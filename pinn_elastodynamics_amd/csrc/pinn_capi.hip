@@ -373,7 +373,7 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
     a.head = head;
     a.din = din;
     a.second = (din == 3 && ns == 5) ? 1 : 0;
-    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head == HEAD_SCORE;
+    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head);
     int pass = 0;
     for (long p0 = 0; p0 < c.n; p0 += mmax, ++pass) {
         a.p0 = p0;
@@ -415,6 +415,15 @@ static void set_hooke(Call& c, double E, double mu, double rho, int plane_strain
     }
     c.c1 = (float)c1;
     c.c2 = (float)c2;
+    c.G = (float)(E / (2.0 * (1.0 + mu)));
+    c.rho = (float)rho;
+}
+
+// isotropic 3-D law (oracle/nc3d_oracle.py): c1 = lambda + 2G, c2 = lambda
+static void hooke3d(Call& c, double E, double mu, double rho) {
+    const double coef = E / ((1.0 + mu) * (1.0 - 2.0 * mu));
+    c.c1 = (float)(coef * (1.0 - mu));
+    c.c2 = (float)(coef * mu);
     c.G = (float)(E / (2.0 * (1.0 + mu)));
     c.rho = (float)rho;
 }
@@ -684,6 +693,25 @@ int pinn_plate2d_loss_grad(const float* params_flat, const int* layers, int n_la
     return impl->plate_loss_grad(c);
 }
 
+int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
+                                int64_t n, const double lb[3], const double ub[3], int normalize, const float* frozen_streams, double E,
+                                double mu, double rho, const float term_weights[5], float* score_out, int precision_mode, void* workspace,
+                                size_t ws_bytes, void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (!term_weights || (n > 0 && (!frozen_streams || !score_out))) return PINN_ERR_NULL;
+    if (c.net.nout != 5) return PINN_ERR_LAYERS;
+    set_hooke(c, E, mu, rho, 0);                       // plane stress, PLATE:416-418: the expressions of pinn_plate2d_loss_grad
+    for (int i = 0; i < 5; ++i) c.tw[i] = term_weights[i];
+    c.aux = frozen_streams;
+    c.fields_out = score_out;
+    if (n == 0) return PINN_OK;
+    if (!impl) return fp32_call(c, HEAD_SCORE_PLATE, 0, 5, 3, false);
+    return impl->plate_score(c);
+}
+
 int pinn_plate2d_traction_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y,
                                     const float* t, int64_t n, const double lb[3], const double ub[3], int normalize,
                                     const float* frozen_and_normals, const float weights[2], float* loss_terms_out,
@@ -858,11 +886,7 @@ int pinn_nc3d_loss_grad(const float* params_flat, const int* layers, int n_layer
     if (rc) return rc;
     if (!term_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
     if (c.net.nout != 12) return PINN_ERR_LAYERS;
-    const double coef = E / ((1.0 + mu) * (1.0 - 2.0 * mu));       // isotropic law: c1 = lambda + 2G, c2 = lambda
-    c.c1 = (float)(coef * (1.0 - mu));
-    c.c2 = (float)(coef * mu);
-    c.G = (float)(E / (2.0 * (1.0 + mu)));
-    c.rho = (float)rho;
+    hooke3d(c, E, mu, rho);
     for (int i = 0; i < 12; ++i) c.tw[i] = term_weights[i];
     c.loss_out = loss_terms_out;
     c.grad_out = grad_flat_out;
@@ -870,6 +894,24 @@ int pinn_nc3d_loss_grad(const float* params_flat, const int* layers, int n_layer
     if (n == 0) return empty_batch(c, 12);
     if (!impl) return fp32_call(c, HEAD_NC3D, 12, 5, 4);
     return impl->nc3d_loss_grad(c);
+}
+
+int pinn_nc3d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
+                             const float* t, int64_t n, const double lb[4], const double ub[4], int normalize, double E, double mu, double rho,
+                             const float term_weights[12], float* score_out, int precision_mode, void* workspace, size_t ws_bytes,
+                             void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
+    if (rc) return rc;
+    if (!term_weights || (n > 0 && !score_out)) return PINN_ERR_NULL;
+    if (c.net.nout != 12) return PINN_ERR_LAYERS;
+    hooke3d(c, E, mu, rho);
+    for (int i = 0; i < 12; ++i) c.tw[i] = term_weights[i];
+    c.fields_out = score_out;
+    if (n == 0) return PINN_OK;
+    if (!impl) return fp32_call(c, HEAD_SCORE3D, 0, 5, 4, false);
+    return impl->nc3d_score(c);
 }
 
 int pinn_nc3d_data_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,

@@ -238,9 +238,17 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 // HEAD_DATA3D : HEAD_DATA for the 4-input net (up to 16 outputs);  HEAD_FIELDS3D : HEAD_FIELDS for it (5 streams)
 // HEAD_SCORE  : forward only, 4 streams: one float per point, sum_i tw[i] f_i^2 of the wave residuals (pinn_wave2d_residual_score); written
 //               through `fields_out` as [n].  A score for another family is one more branch of the score block in Chain::run.
+// HEAD_SCORE_PLATE: forward only, 5 streams (value, x, y, t, tt): the same one float per point for the plate family -- the composite P + D*N
+//               from the frozen streams in `aux` as HEAD_PLATE forms it, then sum_i tw[i] f_i^2 of its five plane-stress residuals
+//               (pinn_plate2d_residual_score)
+// HEAD_SCORE3D: forward only, 5 first-order streams, 4 inputs, 12 outputs: the same for the twelve residuals of HEAD_NC3D
+//               (pinn_nc3d_residual_score)
 enum { HEAD_WAVE = 0, HEAD_DATA = 1, HEAD_FIELDS = 2, HEAD_PLATE = 3, HEAD_TRACTION = 4, HEAD_STREAMS = 5, HEAD_NC3D = 6, HEAD_DATA3D = 7,
-       HEAD_FIELDS3D = 8, HEAD_SCORE = 9 };
-__host__ __device__ constexpr bool head_is_3d(int head) { return head == HEAD_NC3D || head == HEAD_DATA3D || head == HEAD_FIELDS3D; }
+       HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11 };
+__host__ __device__ constexpr bool head_is_3d(int head) {
+    return head == HEAD_NC3D || head == HEAD_DATA3D || head == HEAD_FIELDS3D || head == HEAD_SCORE3D;
+}
+__host__ __device__ constexpr bool head_is_score(int head) { return head == HEAD_SCORE || head == HEAD_SCORE_PLATE || head == HEAD_SCORE3D; }
 constexpr int LOSS_SLOTS_3D = 16;     // per-wave loss partials: 8 slots for the reference's heads, 16 for the 3-D ones
 
 struct ChainArgs {
@@ -255,15 +263,15 @@ struct ChainArgs {
     long ntiles;               // tiles in this chunk
     float sx[4], ox[4];        // input map x' = x*sx + ox  (INF:191 when normalising, identity otherwise); 4-input heads: index 2 = z, 3 = t
     float c1, c2, G, rho;      // Hooke coefficients (INF:238-241 / PLATE:416-418) and density
-    float tw[16];              // per-residual (HEAD_WAVE / HEAD_NC3D) or per-output (HEAD_DATA) weights, max-normalised (HEAD_SCORE: as given)
+    float tw[16];              // per-residual (HEAD_WAVE / HEAD_NC3D) or per-output (HEAD_DATA) weights, max-normalised (score heads: as given)
     const float* targets;      // HEAD_DATA: [nout][n] SoA targets or nullptr (= 0)
     uint16_t* S;               // forward-state panels of this chunk
     uint16_t* Z;               // adjoint panels of this chunk
     long S_tile_stride;        // in 16-bit elements
     long Z_tile_stride;
     float* loss_part;          // [total waves][8 or LOSS_SLOTS_3D] per-wave partial sums of squares
-    float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  HEAD_SCORE: [n]
-    const float* aux;          // HEAD_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
+    float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  score heads: [n]
+    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
     float w5[5][8];            // HEAD_STREAMS: per (stream, output) weights, max-normalised
 };
 
@@ -698,7 +706,7 @@ struct Chain {
         const int wpb = blockDim.x >> 6;
         const long gwave = (long)blockIdx.x * wpb + (threadIdx.x >> 6), nwaves = (long)gridDim.x * wpb;
         const int nl = a.net.nl;
-        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || HEAD == HEAD_SCORE;
+        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD);
         constexpr bool SPILL = !FWD_ONLY;
         __shared__ __attribute__((aligned(16))) char spill_lds[4 * 1024];      // one 1 KB transpose record per wave (256-thread blocks)
         char* rec = spill_lds + (threadIdx.x >> 6) * 1024;
@@ -1024,6 +1032,63 @@ struct Chain {
                     float sc = 0.0f;
 #pragma unroll
                     for (int i = 0; i < 7; ++i) sc += a.tw[i] * (f[i] * f[i]);
+                    if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
+                } else if constexpr (HEAD == HEAD_SCORE_PLATE) {
+                    // the plate's score: composite F = P + D*N and the five residuals exactly as HEAD_PLATE forms them (PLATE:383-387,
+                    // 404-439), a second copy like HEAD_SCORE's; outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt)
+                    float D[5][5], F[5][5];
+#pragma unroll
+                    for (int st = 0; st < 5; ++st)
+#pragma unroll
+                        for (int o = 0; o < 5; ++o) {
+                            D[st][o] = a.aux[((long)(0 * 5 + st) * 5 + o) * a.n + pidx[nb]];
+                            F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + pidx[nb]];      // start from P
+                        }
+#pragma unroll
+                    for (int o = 0; o < 5; ++o) {
+                        const float n0 = Y[0][nb][o];
+                        F[0][o] += D[0][o] * n0;
+#pragma unroll
+                        for (int k = 1; k <= 3; ++k) F[k][o] += D[k][o] * n0 + D[0][o] * Y[k][nb][o];
+                        F[4][o] += D[4][o] * n0 + 2.0f * D[3][o] * Y[3][nb][o] + D[0][o] * Y[4][nb][o];
+                    }
+                    const float e11 = F[1][0], e22 = F[2][1], e12 = F[2][0] + F[1][1];
+                    float f[5];
+                    f[0] = F[1][2] + F[2][4] - a.rho * F[4][0];                       // f_u   PLATE:436
+                    f[1] = F[2][3] + F[1][4] - a.rho * F[4][1];                       // f_v   PLATE:437
+                    f[2] = F[0][2] - (a.c1 * e11 + a.c2 * e22);                       // f_s11 PLATE:421
+                    f[3] = F[0][3] - (a.c2 * e11 + a.c1 * e22);                       // f_s22 PLATE:423
+                    f[4] = F[0][4] - a.G * e12;                                       // f_s12 PLATE:422
+                    float sc = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 5; ++i) sc += a.tw[i] * (f[i] * f[i]);
+                    if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
+                } else if constexpr (HEAD == HEAD_SCORE3D) {
+                    // the 3-D score: the twelve residuals of HEAD_NC3D (oracle/nc3d_oracle.py), a second copy; outputs
+                    // (u,v,w, ut,vt,wt, s11,s22,s33, s12,s13,s23); streams (value, d/dx, d/dy, d/dz, d/dt); c1 = lambda+2G, c2 = lambda
+                    const float(&V)[16] = Y[0][nb];
+                    const float(&X)[16] = Y[1][nb];
+                    const float(&Yy)[16] = Y[2][nb];
+                    const float(&Zz)[16] = Y[3][nb];
+                    const float(&T)[16] = Y[4][nb];
+                    const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
+                    const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
+                    float f[12];
+                    f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
+                    f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
+                    f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
+                    f[3] = T[0] - V[3];
+                    f[4] = T[1] - V[4];
+                    f[5] = T[2] - V[5];
+                    f[6] = V[6] - (a.c1 * e11 + a.c2 * (e22 + e33));
+                    f[7] = V[7] - (a.c1 * e22 + a.c2 * (e11 + e33));
+                    f[8] = V[8] - (a.c1 * e33 + a.c2 * (e11 + e22));
+                    f[9] = V[9] - a.G * e12;
+                    f[10] = V[10] - a.G * e13;
+                    f[11] = V[11] - a.G * e23;
+                    float sc = 0.0f;
+#pragma unroll
+                    for (int i = 0; i < 12; ++i) sc += a.tw[i] * (f[i] * f[i]);
                     if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
                 } else {
                     // predict (INF:337-347): write Y and its tangent streams, [NS*nout][n]

@@ -35,11 +35,11 @@ struct Fp32Args {
     float w5[5][8];            // HEAD_STREAMS: weight per (stream, output)
     float w5n[5][8];           // ... divided by the largest: the loss sums of that head are reported weight-normalised
     const float* targets;      // data heads: [nout][n] or nullptr
-    const float* aux;          // HEAD_PLATE: frozen streams [2][5][5][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or nullptr
+    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE: frozen streams [2][5][5][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or nullptr
     float* S;                  // [nl+1][ns][hr][m]: S_0 = inputs and tangent seeds (first din rows), S_l = state behind hidden layer l
     float* Z;                  // [nl+1][ns][hr][m]: Z_l = adjoint of the pre-activations of weight layer l (Z_nl: nout rows)
     float* fsq;                // [FP32_TERMS][m]: squared residuals of the pass
-    float* fields_out;         // fields heads: [ns][nout][n];  HEAD_SCORE: [n]
+    float* fields_out;         // fields heads: [ns][nout][n];  score heads: [n]
     int ns;                    // streams: 1, 4 (value, x, y, t) or 5 (+ tt for din = 3; value, x, y, z, t for din = 4)
     int hr;                    // row stride of S / Z: max(h, 16)
     int head;                  // HEAD_*
@@ -120,6 +120,59 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             f[6] = Y[0][6] - a.G * e12;
             float sc = 0.0f;
             for (int i = 0; i < 7; ++i) sc += a.tw[i] * (f[i] * f[i]);
+            a.fields_out[gp] = sc;
+            continue;
+        }
+        if (a.head == HEAD_SCORE_PLATE) {
+            // pinn_plate2d_residual_score: the composite and the five residuals of HEAD_PLATE below, sum_i tw[i] f_i^2 through fields_out
+            float D[5][5], F[5][5];
+            for (int st = 0; st < 5; ++st)
+                for (int o = 0; o < 5; ++o) {
+                    D[st][o] = a.aux[((long)(0 * 5 + st) * 5 + o) * a.n + gp];
+                    F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + gp];
+                }
+            for (int o = 0; o < 5; ++o) {
+                const float n0 = Y[0][o];
+                F[0][o] += D[0][o] * n0;
+                for (int k = 1; k <= 3; ++k) F[k][o] += D[k][o] * n0 + D[0][o] * Y[k][o];
+                F[4][o] += D[4][o] * n0 + 2.0f * D[3][o] * Y[3][o] + D[0][o] * Y[4][o];
+            }
+            const float e11 = F[1][0], e22 = F[2][1], e12 = F[2][0] + F[1][1];
+            float f[5];
+            f[0] = F[1][2] + F[2][4] - a.rho * F[4][0];
+            f[1] = F[2][3] + F[1][4] - a.rho * F[4][1];
+            f[2] = F[0][2] - (a.c1 * e11 + a.c2 * e22);
+            f[3] = F[0][3] - (a.c2 * e11 + a.c1 * e22);
+            f[4] = F[0][4] - a.G * e12;
+            float sc = 0.0f;
+            for (int i = 0; i < 5; ++i) sc += a.tw[i] * (f[i] * f[i]);
+            a.fields_out[gp] = sc;
+            continue;
+        }
+        if (a.head == HEAD_SCORE3D) {
+            // pinn_nc3d_residual_score: the twelve residuals of HEAD_NC3D below, sum_i tw[i] f_i^2 through fields_out
+            const float* V = Y[0];
+            const float* X = Y[1];
+            const float* Yy = Y[2];
+            const float* Zz = Y[3];
+            const float* T = Y[4];
+            const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
+            const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
+            float f[12];
+            f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
+            f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
+            f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
+            f[3] = T[0] - V[3];
+            f[4] = T[1] - V[4];
+            f[5] = T[2] - V[5];
+            f[6] = V[6] - (a.c1 * e11 + a.c2 * (e22 + e33));
+            f[7] = V[7] - (a.c1 * e22 + a.c2 * (e11 + e33));
+            f[8] = V[8] - (a.c1 * e33 + a.c2 * (e11 + e22));
+            f[9] = V[9] - a.G * e12;
+            f[10] = V[10] - a.G * e13;
+            f[11] = V[11] - a.G * e23;
+            float sc = 0.0f;
+            for (int i = 0; i < 12; ++i) sc += a.tw[i] * (f[i] * f[i]);
             a.fields_out[gp] = sc;
             continue;
         }

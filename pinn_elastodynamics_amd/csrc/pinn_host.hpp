@@ -124,6 +124,9 @@ struct Impl {
     int (*nc3d_fields)(const Call&);
     // per-point residual score of the wave family (forward only, HEAD_SCORE)
     int (*wave_score)(const Call&);
+    // the same for the plate family (HEAD_SCORE_PLATE, `aux` = frozen streams) and the 4-input family (HEAD_SCORE3D); split modes only
+    int (*plate_score)(const Call&);
+    int (*nc3d_score)(const Call&);
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -830,6 +833,28 @@ struct Host {
         return (int)hipGetLastError();
     }
 
+    // pinn_plate2d_residual_score / pinn_nc3d_residual_score: wave_score with five streams; split-precision variants only, like their loss calls
+    template <int HEAD>
+    static int score5(const Call& c) {
+        if constexpr (SPLIT == 3) {
+            Plan p;
+            int rc = make_plan<5>(c, p, false);
+            if (rc) return rc;
+            rc = repack(c, p);
+            if (rc) return rc;
+            ChainArgs a;
+            fill_common(c, p, a);
+            for (int i = 0; i < 16; ++i) a.tw[i] = c.tw[i];
+            a.tile0 = 0;
+            a.ntiles = p.ntiles;
+            hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, nb<5>(), 5, HEAD>), dim3(chain_blocks(p.ntiles)), dim3(256), 0, c.stream, a);
+            return (int)hipGetLastError();
+        }
+        return PINN_ERR_PRECISION;
+    }
+    static int plate_score(const Call& c) { return score5<HEAD_SCORE_PLATE>(c); }
+    static int nc3d_score(const Call& c) { return score5<HEAD_SCORE3D>(c); }
+
     // 5-stream family (plate): split-precision variants only
     static int plate_loss_grad(const Call& c) {
         if constexpr (SPLIT == 3) {
@@ -1035,7 +1060,7 @@ struct Host {
     static const Impl* impl() {
         static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
                                &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
-                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score};
+                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score};
         return &I;
     }
 };

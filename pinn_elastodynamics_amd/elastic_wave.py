@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from .net_api import NetApi, read_checkpoint, truncated_normal, write_checkpoint
+from .refine import candidate_array, pair_replacements, refine_sharded_set, score_weights  # noqa: F401
 
 # multipliers of (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss_NB, loss_FIX) in the total loss
 LOSS_LAYOUT = {
@@ -255,18 +256,6 @@ def lbfgs_hip(engine, theta, evaluate, n_params, loss_coeffs, options, callback=
                        success=rec["status"] in (1, 2), max_abs_grad=rec["max_abs_grad"], pairs=rec["pairs"], skipped=rec["skipped"])
 
 
-def pair_replacements(cand_idx, cand_score, row_idx, row_score):
-    """The pairing rule of refine_collocation on the K selected candidates and the K selected rows (torch tensors on any device; the index
-    tensors ascending, as select_k returns them): candidates by score descending, rows by score ascending -- ties by index ascending in
-    both --, pair j = (row j, candidate j), kept ONLY where the candidate's score is strictly larger than the row's.  A NaN score never
-    satisfies that.  Returns (rows, candidates, row scores, candidate scores) of the kept pairs, in pairing order."""
-    oc = torch.sort(cand_score, descending=True, stable=True).indices
-    orr = torch.sort(row_score, descending=False, stable=True).indices
-    ci, cs, ri, rs = cand_idx[oc], cand_score[oc], row_idx[orr], row_score[orr]
-    keep = cs > rs
-    return ri[keep], ci[keep], rs[keep], cs[keep]
-
-
 class DeepHPM(NetApi):
     """Drop-in for the reference's model class on the wave cases (INF:21-376)."""
 
@@ -471,12 +460,7 @@ class DeepHPM(NetApi):
     # ------------------------------------------------------------------------------------------
     def _score_weights(self, weights):
         """the coefficients the case's LOSS_LAYOUT puts on the seven collocation terms, unless the caller gives seven of its own"""
-        if weights is None:
-            return [self.layout["f_uv"]] * 4 + [self.layout["f_s"]] * 3
-        w = [float(v) for v in np.asarray(weights, dtype=np.float64).reshape(-1)]
-        if len(w) != 7:
-            raise ValueError("weights: one per residual of net_f_sig (f_u, f_v, f_ut, f_vt, f_s11, f_s22, f_s12)")
-        return w
+        return score_weights(weights, [self.layout["f_uv"]] * 4 + [self.layout["f_s"]] * 3, "(f_u, f_v, f_ut, f_vt, f_s11, f_s22, f_s12)")
 
     def _score_device(self, xs, w, packed=False):
         kw = {"packed": True} if packed else {}
@@ -500,39 +484,8 @@ class DeepHPM(NetApi):
         Returns dict(replaced, rows, candidate_indices, score_replaced_max, score_inserted_min): how many rows changed, their row numbers in the
         whole set and the candidates that took their places (pairing order), the largest score that left and the smallest that came in (None
         when nothing was replaced).  Synchronises once (the indices come to the host)."""
-        C = np.asarray(candidates, dtype=np.float64)
-        if C.ndim != 2 or C.shape[1] != 3:
-            raise ValueError("candidates must be [Nc, 3] = (x, y, t)")
-        w = self._score_weights(weights)
-        s0, e0 = self._shard(0, self._n_collo)
-        K = min(int(n_replace), C.shape[0], e0 - s0)
-        out = {"replaced": 0, "rows": np.zeros(0, dtype=np.int64), "candidate_indices": np.zeros(0, dtype=np.int64),
-               "score_replaced_max": None, "score_inserted_min": None}
-        if K <= 0:
-            return out
-        rows = self._rows(0, self._n_collo)
-        cand = tuple(torch.from_numpy(np.ascontiguousarray(C[:, k], dtype=np.float32)).to(self.device) for k in range(3))
-        s_rows = self._score_device(rows, w)
-        s_cand = self._score_device(cand, w, packed=True)
-        ci = self.engine.select_k(s_cand, K, largest=True).long()
-        ri = self.engine.select_k(s_rows, K, largest=False).long()
-        ri, ci, rs, cs = pair_replacements(ci, s_cand[ci], ri, s_rows[ri])
-        m = int(ri.numel())
-        self._collo_cache = {}
-        if m == 0:
-            return out
-        if self._collo_full is not None:
-            for k in range(3):
-                self._collo_full[k][s0 + ri] = cand[k][ci]
-        r_host, c_host = ri.cpu().numpy() + s0, ci.cpu().numpy()
-        if not getattr(self, "_collo_cols_owned", False):      # (x_c, y_c, t_c may be views of the caller's array: write to copies)
-            self.x_c, self.y_c, self.t_c = self.x_c.copy(), self.y_c.copy(), self.t_c.copy()
-            self._collo_cols_owned = True
-        for k, col in enumerate((self.x_c, self.y_c, self.t_c)):
-            col[r_host, 0] = C[c_host, k]
-            self._collo_host[k][r_host] = C[c_host, k].astype(np.float32)
-        out.update(replaced=m, rows=r_host, candidate_indices=c_host, score_replaced_max=float(rs.max()), score_inserted_min=float(cs.min()))
-        return out
+        C = candidate_array(candidates, 3, "(x, y, t)")
+        return refine_sharded_set(self, C, n_replace, self._score_weights(weights), ("x_c", "y_c", "t_c"))
 
     def callback(self, loss):                        # INF:278-280, SEMI:285-288
         self.count = self.count + 1

@@ -273,6 +273,38 @@ class HipEngine(LbfgsMixin):
                                        self._ws_ptr, self.ws_bytes, self._stream())
         return out
 
+    def plate_residual_score(self, params, x, y, t, lb, ub, normalize, frozen, term_weights, E=20.0, mu=0.25, rho=1.0,
+                             out: Optional[torch.Tensor] = None, packed: bool = False):
+        """The same for the plate family (pinn_plate2d_residual_score): ``frozen`` is the [2, 5, 5, n] tensor of plate_loss_grad at these points,
+        the five residuals are those of the composite P + D*N.  Returns the device tensor [n]."""
+        n = x.numel()
+        for v in (x, y, t):
+            self._chk(v, n)
+        self._chk(params, self.n_params)
+        self._chk(frozen, 50 * n)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._chk(out, n)
+        self.lib.plate2d_residual_score(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
+                                        frozen.data_ptr(), E, mu, rho, term_weights, out.data_ptr(),
+                                        PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr, self.ws_bytes, self._stream())
+        return out
+
+    def nc3d_residual_score(self, params, x, y, z, t, lb, ub, normalize, term_weights, E=2.5, mu=0.25, rho=1.0,
+                            out: Optional[torch.Tensor] = None, packed: bool = False):
+        """The same for the 4-input family (pinn_nc3d_residual_score): the twelve residuals of nc3d_loss_grad.  Returns the device tensor [n]."""
+        n = x.numel()
+        for v in (x, y, z, t):
+            self._chk(v, n)
+        self._chk(params, self.n_params)
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._chk(out, n)
+        self.lib.nc3d_residual_score(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), z.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
+                                     E, mu, rho, term_weights, out.data_ptr(), PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr,
+                                     self.ws_bytes, self._stream())
+        return out
+
     def select_k(self, score, k: int, largest: bool = True):
         """The k largest (or smallest) entries of the device tensor ``score`` as a device int32 [k] of ASCENDING indices (pinn_select_k):
         ties go to the lowest index, a NaN ranks above +inf, the result is exactly reproducible.  No synchronisation."""

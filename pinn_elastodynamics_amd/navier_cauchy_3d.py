@@ -19,6 +19,7 @@ import torch
 
 from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, unpack_params, xavier_init  # noqa: F401
 from .net_api import NetApi, read_checkpoint, write_checkpoint
+from .refine import candidate_array, refine_sharded_set, score_weights
 
 OUT = ("u", "v", "w", "ut", "vt", "wt", "s11", "s22", "s33", "s12", "s13", "s23")
 _SLOTS = ("collo", "IC", "SRC", "NB")          # 16 floats each in the loss-sum buffer
@@ -187,6 +188,32 @@ class NavierCauchy3D(NetApi):
 
     net_uvp = net_uv
     net_f = net_f_sig
+
+    # ---- residual-adaptive refinement of the collocation set (refine.py) ----------------------------------------------
+    def _score_weights(self, weights):
+        """the coefficients the loss layout puts on the twelve collocation terms, unless the caller gives twelve of its own"""
+        return score_weights(weights, [self.layout["f_uv"]] * 6 + [self.layout["f_s"]] * 6,
+                             "(f_u, f_v, f_w, f_ut, f_vt, f_wt, f_s11, f_s22, f_s33, f_s12, f_s13, f_s23)")
+
+    def _score_device(self, xs, w, packed=False):
+        kw = {"packed": True} if packed else {}
+        return self.engine.nc3d_residual_score(self.theta, xs[0], xs[1], xs[2], xs[3], self.lb, self.ub, self.normalize, w, self.E, self.mu,
+                                               self.rho, **kw)
+
+    def residual_score(self, x, y, z, t, weights=None):
+        """sum_i weights[i] * f_i^2 of net_f_sig's twelve residuals per point, numpy [N,1], formed on the device: the measure
+        refine_collocation ranks by.  Default ``weights``: what the loss layout puts on the collocation terms."""
+        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, z, t)]
+        return self._score_device(xs, self._score_weights(weights)).detach().cpu().numpy().reshape(-1, 1)
+
+    def refine_collocation(self, candidates, n_replace, weights=None):
+        """Residual-adaptive refinement that keeps the set's size, exactly as elastic_wave.DeepHPM.refine_collocation with four columns:
+        ``candidates`` [Nc,4] (x, y, z, t); the K = min(n_replace, Nc, rows) lowest-scoring rows of this rank give way to the K highest-scoring
+        candidates where those score strictly higher.  N, the 1/N weights, the block boundaries of train(batch_num), the workspace and the
+        shards stay; the host copies (x_c, y_c, z_c, t_c) follow on copies.  Data parallel: no collective, pass rank-distinct candidates.
+        Returns dict(replaced, rows, candidate_indices, score_replaced_max, score_inserted_min).  Synchronises once."""
+        C = candidate_array(candidates, 4, "(x, y, z, t)")
+        return refine_sharded_set(self, C, n_replace, self._score_weights(weights), ("x_c", "y_c", "z_c", "t_c"))
 
     def callback(self, loss):
         self.count += 1

@@ -18,6 +18,7 @@ import torch
 
 from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, relax_adjoint_shift, unpack_params, xavier_init  # noqa: F401
 from .net_api import NetApi, read_checkpoint, write_checkpoint
+from .refine import candidate_array, device_columns, empty_result, score_weights, select_pairs, update_host_columns
 
 _EPS = float(np.finfo(float).eps)
 BFGS_OPTIONS = {   # PLATE:220-247
@@ -241,6 +242,65 @@ class PINN(NetApi):
     def net_t(self, x, y, t):                        # PLATE:452-461
         x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
         return self.net_surf_var(x, y, t, -x / self.hole_r, -y / self.hole_r)
+
+    # ---- residual-adaptive refinement of the collocation set (refine.py) ----------------------------------------------
+    def _score_weights(self, weights):
+        """10 on each of the five collocation terms -- what loss = 10 (...) puts on them without the 1/N --, unless the caller gives five"""
+        return score_weights(weights, [10.0] * 5, "(f_u, f_v, f_s11, f_s22, f_s12)")
+
+    def _frozen_at(self, xs):
+        """[2, 5, 5, n]: the streams of the frozen distance and particular nets at the device columns ``xs``"""
+        D = self.eng["dist"].net_streams(self.theta["dist"], xs[0], xs[1], xs[2], self.lb, self.ub, False)
+        P = self.eng["part"].net_streams(self.theta["part"], xs[0], xs[1], xs[2], self.lb, self.ub, False)
+        return torch.stack([D, P]).contiguous()
+
+    def _score_device(self, xs, frozen, w, packed=False):
+        kw = {"packed": True} if packed else {}
+        return self.eng["uv"].plate_residual_score(self.theta["uv"], xs[0], xs[1], xs[2], self.lb, self.ub, False, frozen, w, self.E, self.mu,
+                                                   self.rho, **kw)
+
+    def residual_score(self, x, y, t, weights=None):
+        """sum_i weights[i] * f_i^2 of net_f_sig's five residuals (PLATE:404-439) per point, numpy [N,1]: the D and P streams at the points,
+        then one score call on the uv net that forms the composite and the residuals in the kernel.  Default ``weights``: [10] * 5."""
+        w = self._score_weights(weights)
+        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, t)]
+        if xs[0].numel() == 0:
+            return np.zeros((0, 1), dtype=np.float32)
+        return self._score_device(xs, self._frozen_at(xs), w).detach().cpu().numpy().reshape(-1, 1)
+
+    def refine_collocation(self, candidates, n_replace, weights=None):
+        """Residual-adaptive refinement that keeps the set's size (the rule of elastic_wave.DeepHPM.refine_collocation): score this rank's rows
+        with the frozen streams it holds and the ``candidates`` [Nc,3] (x, y, t) with frozen streams computed once for them; the
+        K = min(n_replace, Nc, rows) lowest-scoring rows give way to the K highest-scoring candidates where those score strictly higher.
+        THE FROZEN STREAMS FOLLOW THE ROW: for every replaced row the three coordinate columns AND the [2,5,5] column of the frozen D / P
+        streams are overwritten with the candidate's, gathered on the device -- no second evaluation of the frozen nets.  The streams of a
+        point do not depend on its place in the batch (a point is one row of a tile), so refresh_frozen() afterwards gives the same bits
+        (tests/test_gpu_refine_families.py holds that).  n_collo, the 1/N weights, the workspace and the shards stay; x_c, y_c, t_c follow on
+        copies.  Data parallel: no collective, every rank refines its own rows: pass rank-distinct candidates.
+        Returns dict(replaced, rows, candidate_indices, score_replaced_max, score_inserted_min) like DeepHPM's; ``rows`` are row numbers of
+        the whole set.  Synchronises once."""
+        C = candidate_array(candidates, 3, "(x, y, t)")
+        w = self._score_weights(weights)
+        s0, e0 = self._shard(0, self.n_collo)
+        K = min(int(n_replace), C.shape[0], e0 - s0)
+        out = empty_result()
+        if K <= 0:
+            return out
+        cand = device_columns(C, self.device)
+        frozen_cand = self._frozen_at(cand)
+        s_rows = self._score_device(self._collo, self._frozen_collo, w)
+        s_cand = self._score_device(cand, frozen_cand, w, packed=True)
+        ri, ci, rs, cs = select_pairs(self.eng["uv"], s_rows, s_cand, K)
+        m = int(ri.numel())
+        if m == 0:
+            return out
+        for k in range(3):
+            self._collo[k][ri] = cand[k][ci]
+        self._frozen_collo[..., ri] = frozen_cand[..., ci]
+        r_host, c_host = ri.cpu().numpy() + s0, ci.cpu().numpy()
+        update_host_columns(self, ("x_c", "y_c", "t_c"), r_host, c_host, C)
+        out.update(replaced=m, rows=r_host, candidate_indices=c_host, score_replaced_max=float(rs.max()), score_inserted_min=float(cs.min()))
+        return out
 
     def callback(self, loss):
         self.count = self.count + 1
