@@ -112,13 +112,6 @@ bool xcd_tail_device_ok() {
 }
 }
 
-template <class F>
-static int cache_policy_of(size_t* images, size_t* sums) {
-    if (images) *images = F::IMAGES_WG_BYTES;
-    if (sums) *sums = F::SUMS_WG_BYTES;
-    return F::NT_SUMS ? 1 : (F::NT_IMAGES ? 2 : 0);
-}
-
 extern "C" {
 
 int pinn_abi_version(void) { return 2; }      // 2 (round 6): PINN_IPC_HANDLE_BYTES 64 -> 128, pinn_p2p_set_timeout_ms / _peek_status, pinn_wave2d_step_checked
@@ -184,27 +177,9 @@ int pinn_debug_cache_policy(const int* layers, int n_layers, int head, size_t* i
     int width = 0;
     const int rc = decode_net(layers, n_layers, net, width, din);
     if (rc) return rc;
-    // (the instantiations the f16x3 families ship: pinn_host.hpp, Host::fused_depth / fused_has_3d)
-    if (head == PINN_HEAD_NC3D) {
-        if (width == 128 && net.nl == 10 && net.nout == 12) return cache_policy_of<Fused<OpF16, 3, 128, 10, 5, false, 4>>(images_bytes, sums_bytes);
-        return PINN_ERR_LAYERS;
-    }
-    if (head == PINN_HEAD_PLATE) {
-        if (width == 32 && net.nl == 4) return cache_policy_of<Fused<OpF16, 3, 32, 4, 5>>(images_bytes, sums_bytes);
-        if (width == 64 && net.nl == 4) return cache_policy_of<Fused<OpF16, 3, 64, 4, 5>>(images_bytes, sums_bytes);
-        if (width == 64 && net.nl == 8) return cache_policy_of<Fused<OpF16, 3, 64, 8, 5>>(images_bytes, sums_bytes);
-        if (width == 96 && net.nl == 8) return cache_policy_of<Fused<OpF16, 3, 96, 8, 5>>(images_bytes, sums_bytes);
-        return PINN_ERR_LAYERS;
-    }
-    if (head != PINN_HEAD_WAVE) return PINN_ERR_LAYERS;
-    if (width == 32 && net.nl == 4) return cache_policy_of<Fused<OpF16, 3, 32, 4, 4>>(images_bytes, sums_bytes);
-    if (width == 32 && net.nl == 8) return cache_policy_of<Fused<OpF16, 3, 32, 8, 4>>(images_bytes, sums_bytes);
-    if (width == 64 && net.nl == 4) return cache_policy_of<Fused<OpF16, 3, 64, 4, 4>>(images_bytes, sums_bytes);
-    if (width == 64 && net.nl == 8) return cache_policy_of<Fused<OpF16, 3, 64, 8, 4>>(images_bytes, sums_bytes);
-    if (width == 96 && net.nl == 8) return cache_policy_of<Fused<OpF16, 3, 96, 8, 4>>(images_bytes, sums_bytes);
-    if (width == 128 && net.nl == 8) return cache_policy_of<Fused<OpF16, 3, 128, 8, 4>>(images_bytes, sums_bytes);
-    if (width == 160 && net.nl == 6) return cache_policy_of<Fused<OpF16, 3, 160, 6, 4>>(images_bytes, sums_bytes);
-    return PINN_ERR_LAYERS;
+    // (the collocation kernels the f16x3 families ship: Host::with_fused of the F16 split-3 line of this width)
+    const Impl* impl = find_impl(PINN_PREC_F16X3, width);
+    return impl ? impl->cache_policy(net, head, images_bytes, sums_bytes) : PINN_ERR_LAYERS;
 }
 
 int pinn_debug_set_fused_grid_cap(int cap) { const int old = g_fused_grid_cap; g_fused_grid_cap = cap < 0 ? 0 : cap; return old; }
@@ -359,10 +334,7 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
     a.rho = c.rho;
     for (int i = 0; i < 16; ++i) a.tw[i] = c.tw[i];
     // stream-wise data head: the loss sums are reported weight-normalised like the 16-bit kernels do (sum_s w[s][o] / max|w| d^2)
-    float wmax = 0.0f;
-    for (int i = 0; i < 5; ++i)
-        for (int o = 0; o < 8; ++o) { const float v = c.w5[i][o] < 0 ? -c.w5[i][o] : c.w5[i][o]; if (v > wmax) wmax = v; }
-    if (c.w5_norm > 0.0f) wmax = c.w5_norm;      // (a set of pinn_stream_loss_grad_multi: the call's one maximum)
+    const float wmax = c.w5_norm > 0.0f ? c.w5_norm : max_abs(&c.w5[0][0], 40);      // (w5_norm: a set of pinn_stream_loss_grad_multi, the call's one maximum)
     for (int i = 0; i < 5; ++i)
         for (int o = 0; o < 8; ++o) { a.w5[i][o] = c.w5[i][o]; a.w5n[i][o] = wmax > 0.0f ? c.w5[i][o] / wmax : 0.0f; }
     a.targets = c.targets;
@@ -395,14 +367,82 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
     return PINN_OK;
 }
 
-// lr_t of the TF1 rule (bias correction folded into the step size, computed in double)
+// lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) of the TF1 AdamOptimizer (bias correction folded into the step size, computed in double):
+// pinn_adam_step and the Adam epilogue of the step calls take it from here, so they update with the same bits
 static float adam_lr_t(double lr, double beta1, double beta2, int64_t step) {
-    const double b1t = __builtin_pow(beta1, (double)step), b2t = __builtin_pow(beta2, (double)step);      // (pinn_adam_step's own expression: the same bits)
+    const double b1t = __builtin_pow(beta1, (double)step), b2t = __builtin_pow(beta2, (double)step);
     const double lr_t = lr * __builtin_sqrt(1.0 - b2t) / (1.0 - b1t);
     return (float)lr_t;
 }
 
-// Hooke coefficients: plane strain INF:238-241, plane stress PLATE:416-418
+// ---- the optional Adam update of the step calls: argument check, the epilogue of the one-launch form, and the tail of every other case
+static int check_adam(const pinn_adam_state* adam) {
+    if (adam && (!adam->m || !adam->v || adam->step < 1)) return adam->step < 1 ? PINN_ERR_SIZE : PINN_ERR_NULL;
+    return PINN_OK;
+}
+static AdamEpilogue adam_epilogue(float* params_flat, const pinn_adam_state* adam) {
+    if (!adam) return AdamEpilogue{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f};
+    return AdamEpilogue{params_flat, adam->m, adam->v, adam_lr_t(adam->lr, adam->beta1, adam->beta2, adam->step), (float)adam->beta1, (float)adam->beta2, (float)adam->eps};
+}
+static int adam_tail(float* params_flat, const int* layers, int n_layers, const float* grad_flat, const pinn_adam_state* adam, void* stream) {
+    if (!adam) return PINN_OK;
+    NetDesc net;
+    int width = 0;
+    const int rc = decode_net(layers, n_layers, net, width, 3);
+    if (rc) return rc;
+    return pinn_adam_step(params_flat, adam->m, adam->v, grad_flat, net.nparams, adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, stream);
+}
+
+// ---- the value-only sets of pinn_data_loss_grad_multi / pinn_wave2d_step: set by set, a negative size before a missing pointer
+static int check_point_sets(const pinn_point_set* sets, int n_sets) {
+    for (int k = 0; k < n_sets; ++k) {
+        if (sets[k].n < 0) return PINN_ERR_SIZE;
+        if (!sets[k].loss_terms_out || (sets[k].n > 0 && (!sets[k].x || !sets[k].y || !sets[k].t))) return PINN_ERR_NULL;
+    }
+    return PINN_OK;
+}
+static void copy_point_sets(const pinn_point_set* sets, int n_sets, Call& c) {
+    c.nsets = n_sets;
+    for (int k = 0; k < n_sets; ++k) {
+        c.sets[k].x = sets[k].x;
+        c.sets[k].y = sets[k].y;
+        c.sets[k].t = sets[k].t;
+        c.sets[k].targets = sets[k].targets;
+        c.sets[k].n = (long)sets[k].n;
+        for (int i = 0; i < 8; ++i) c.sets[k].tw[i] = i < c.net.nout ? sets[k].out_weights[i] : 0.0f;
+        c.sets[k].loss_out = sets[k].loss_terms_out;
+    }
+}
+// empty sets report zero sums
+static int zero_empty_sets(const pinn_point_set* sets, int n_sets, int nout, hipStream_t st) {
+    for (int k = 0; k < n_sets; ++k) {
+        const int rc = sets[k].n == 0 ? (int)hipMemsetAsync(sets[k].loss_terms_out, 0, (size_t)nout * sizeof(float), st) : 0;
+        if (rc) return rc;
+    }
+    return PINN_OK;
+}
+
+// ---- the common end of the single-set entry points, behind prepare() and the entry's own checks: the outputs, the empty batch, then
+// PINN_PREC_FP32 (impl == NULL: fp32_call with the head's streams `ns`) or the kernel family's call
+static int run_loss_grad(Call& c, const Impl* impl, float* loss_out, float* grad_out, int accumulate, int nterms, int (*Impl::*call)(const Call&),
+                         int head, int ns, int din = 3) {
+    c.loss_out = loss_out;
+    c.grad_out = grad_out;
+    c.accumulate = accumulate;
+    if (c.n == 0) return empty_batch(c, nterms);
+    if (!impl) return fp32_call(c, head, nterms, ns, din);
+    return (impl->*call)(c);
+}
+// (forward only: fields, streams and the residual scores -- the scores are no loss + gradient calls and not counted as a path)
+static int run_forward(Call& c, const Impl* impl, float* out, int (*Impl::*call)(const Call&), int head, int ns, int din = 3) {
+    c.fields_out = out;
+    if (c.n == 0) return PINN_OK;
+    if (!impl) return fp32_call(c, head, 0, ns, din, !head_is_score(head));
+    return (impl->*call)(c);
+}
+
+// Hooke coefficients: plane strain INF:238-241 -- also the isotropic 3-D law, c1 = lambda + 2G, c2 = lambda (oracle/nc3d_oracle.py) --, plane
+// stress PLATE:416-418.  Evaluated in double, each cast to float once.
 static void set_hooke(Call& c, double E, double mu, double rho, int plane_strain) {
     double c1, c2;
     if (plane_strain) {
@@ -419,15 +459,6 @@ static void set_hooke(Call& c, double E, double mu, double rho, int plane_strain
     c.rho = (float)rho;
 }
 
-// isotropic 3-D law (oracle/nc3d_oracle.py): c1 = lambda + 2G, c2 = lambda
-static void hooke3d(Call& c, double E, double mu, double rho) {
-    const double coef = E / ((1.0 + mu) * (1.0 - 2.0 * mu));
-    c.c1 = (float)(coef * (1.0 - mu));
-    c.c2 = (float)(coef * mu);
-    c.G = (float)(E / (2.0 * (1.0 + mu)));
-    c.rho = (float)rho;
-}
-
 static int wave2d_loss_grad_impl(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                           int64_t n, const double lb[3], const double ub[3], int normalize, double E, double mu, double rho,
                           int plane_strain, const float term_weights[7], float* loss_terms_out, float* grad_flat_out, int accumulate,
@@ -440,13 +471,8 @@ static int wave2d_loss_grad_impl(const float* params_flat, const int* layers, in
     if (c.net.nout != 7) return PINN_ERR_LAYERS;
     set_hooke(c, E, mu, rho, plane_strain);
     for (int i = 0; i < 7; ++i) c.tw[i] = term_weights[i];
-    c.loss_out = loss_terms_out;
-    c.grad_out = grad_flat_out;
-    c.accumulate = accumulate;
     if (prof_ms) c.prof_ms = prof_ms;
-    if (n == 0) return empty_batch(c, 7);
-    if (!impl) return fp32_call(c, HEAD_WAVE, 7, 4);
-    return impl->wave_loss_grad(c);
+    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 7, &Impl::wave_loss_grad, HEAD_WAVE, 4);
 }
 
 int pinn_wave2d_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
@@ -477,71 +503,45 @@ int pinn_data_loss_grad(const float* params_flat, const int* layers, int n_layer
     if (!out_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
     for (int i = 0; i < c.net.nout; ++i) c.tw[i] = out_weights[i];
     c.targets = targets;
-    c.loss_out = loss_terms_out;
-    c.grad_out = grad_flat_out;
-    c.accumulate = accumulate;
-    if (n == 0) return empty_batch(c, c.net.nout);
-    if (!impl) return fp32_call(c, HEAD_DATA, c.net.nout, 1);
-    return impl->data_loss_grad(c);
+    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, c.net.nout, &Impl::data_loss_grad, HEAD_DATA, 1);
 }
 
 int pinn_data_loss_grad_multi(const float* params_flat, const int* layers, int n_layers, const pinn_point_set* sets, int n_sets,
                               const double lb[3], const double ub[3], int normalize, float* grad_flat_out, int accumulate, int precision_mode,
                               void* workspace, size_t ws_bytes, void* stream) {
     if (!sets || n_sets < 1 || n_sets > PINN_MAX_SETS || !grad_flat_out) return n_sets < 1 || n_sets > PINN_MAX_SETS ? PINN_ERR_SIZE : PINN_ERR_NULL;
+    int rc = check_point_sets(sets, n_sets);
+    if (rc) return rc;
     int64_t nmax = 0, ntot = 0;
     const pinn_point_set* first = nullptr;
     for (int k = 0; k < n_sets; ++k) {
-        if (sets[k].n < 0) return PINN_ERR_SIZE;
-        if (!sets[k].loss_terms_out || (sets[k].n > 0 && (!sets[k].x || !sets[k].y || !sets[k].t))) return PINN_ERR_NULL;
         if (sets[k].n > 0 && !first) first = &sets[k];
         if (sets[k].n > nmax) nmax = sets[k].n;
         ntot += sets[k].n;
     }
     Call c;
     const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, first ? first->x : nullptr, first ? first->y : nullptr, first ? first->t : nullptr, nmax, lb, ub,
-                     normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    rc = prepare(params_flat, layers, n_layers, first ? first->x : nullptr, first ? first->y : nullptr, first ? first->t : nullptr, nmax, lb, ub,
+                 normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
     if (rc) return rc;
     c.grad_out = grad_flat_out;
     c.accumulate = accumulate;
-    c.targets = nullptr;
-    c.nsets = n_sets;
+    copy_point_sets(sets, n_sets, c);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int k = 0; k < n_sets; ++k) {
-        c.sets[k].x = sets[k].x;
-        c.sets[k].y = sets[k].y;
-        c.sets[k].t = sets[k].t;
-        c.sets[k].targets = sets[k].targets;
-        c.sets[k].n = (long)sets[k].n;
-        for (int i = 0; i < 8; ++i) c.sets[k].tw[i] = i < c.net.nout ? sets[k].out_weights[i] : 0.0f;
-        c.sets[k].loss_out = sets[k].loss_terms_out;
-        if (sets[k].n == 0 && (rc = (int)hipMemsetAsync(sets[k].loss_terms_out, 0, (size_t)c.net.nout * sizeof(float), st))) return rc;
-    }
+    if ((rc = zero_empty_sets(sets, n_sets, c.net.nout, st))) return rc;
     if (ntot == 0) {
         if (!accumulate) return (int)hipMemsetAsync(grad_flat_out, 0, (size_t)c.net.nparams * sizeof(float), st);
         return 0;
     }
-    if (!impl) {            // PINN_PREC_FP32: one set after the other into the same gradient
-        bool first_set = true;
-        for (int k = 0; k < n_sets; ++k) {
-            if (sets[k].n <= 0) continue;
-            Call s1 = c;
-            s1.nsets = 0;
-            s1.x = sets[k].x;
-            s1.y = sets[k].y;
-            s1.t = sets[k].t;
-            s1.n = (long)sets[k].n;
-            s1.targets = sets[k].targets;
-            for (int i = 0; i < 8; ++i) s1.tw[i] = c.sets[k].tw[i];
-            s1.loss_out = sets[k].loss_terms_out;
-            s1.accumulate = accumulate || !first_set;
-            if ((rc = fp32_call(s1, HEAD_DATA, c.net.nout, 1))) return rc;
-            first_set = false;
-        }
-        return PINN_OK;
+    if (impl) return impl->data_loss_grad(c);
+    // PINN_PREC_FP32: one set after the other into the same gradient
+    bool first_set = true;
+    for (int k = 0; k < n_sets; ++k) {
+        if (sets[k].n <= 0) continue;
+        if ((rc = fp32_call(set_call(c, c.sets[k], first_set), HEAD_DATA, c.net.nout, 1))) return rc;
+        first_set = false;
     }
-    return impl->data_loss_grad(c);
+    return PINN_OK;
 }
 
 int pinn_wave2d_step(float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
@@ -550,18 +550,16 @@ int pinn_wave2d_step(float* params_flat, const int* layers, int n_layers, const 
                      int accumulate, const pinn_adam_state* adam, int precision_mode, void* workspace, size_t ws_bytes, void* stream) {
     if (n_sets < 0 || n_sets > PINN_MAX_SETS) return PINN_ERR_SIZE;
     if (n_sets > 0 && !sets) return PINN_ERR_NULL;
-    if (adam && (!adam->m || !adam->v || adam->step < 1)) return adam->step < 1 ? PINN_ERR_SIZE : PINN_ERR_NULL;
+    int rc = check_adam(adam);
+    if (!rc) rc = check_point_sets(sets, n_sets);
+    if (rc) return rc;
     int64_t side_total = 0;
-    for (int k = 0; k < n_sets; ++k) {
-        if (sets[k].n < 0) return PINN_ERR_SIZE;
-        if (!sets[k].loss_terms_out || (sets[k].n > 0 && (!sets[k].x || !sets[k].y || !sets[k].t))) return PINN_ERR_NULL;
-        side_total += sets[k].n;
-    }
+    for (int k = 0; k < n_sets; ++k) side_total += sets[k].n;
     // ---- the one-launch form: collocation set and side sets through fused_step_kernel, one reduction (+ Adam) behind it
     if (n > 0 && side_total > 0 && term_weights && loss_terms_out && grad_flat_out) {
         Call c;
         const Impl* impl = nullptr;
-        int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+        rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
         if (rc) return rc;
         if (c.net.nout != 7) return PINN_ERR_LAYERS;
         if (impl) {
@@ -573,30 +571,14 @@ int pinn_wave2d_step(float* params_flat, const int* layers, int n_layers, const 
             Call d = c;
             for (int i = 0; i < 16; ++i) d.tw[i] = 0.0f;
             d.loss_out = nullptr;
-            d.nsets = n_sets;
-            hipStream_t st = static_cast<hipStream_t>(stream);
-            for (int k = 0; k < n_sets; ++k) {
-                d.sets[k].x = sets[k].x;
-                d.sets[k].y = sets[k].y;
-                d.sets[k].t = sets[k].t;
-                d.sets[k].targets = sets[k].targets;
-                d.sets[k].n = (long)sets[k].n;
-                for (int i = 0; i < 8; ++i) d.sets[k].tw[i] = i < c.net.nout ? sets[k].out_weights[i] : 0.0f;
-                d.sets[k].loss_out = sets[k].loss_terms_out;
-            }
-            AdamEpilogue ep = {nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f};
-            if (adam) ep = AdamEpilogue{params_flat, adam->m, adam->v, adam_lr_t(adam->lr, adam->beta1, adam->beta2, adam->step), (float)adam->beta1, (float)adam->beta2, (float)adam->eps};
-            if (impl->wave_step(c, d, ep, &rc)) {
-                if (rc) return rc;
-                for (int k = 0; k < n_sets; ++k)      // (empty sets report zeros, as in pinn_data_loss_grad_multi)
-                    if (sets[k].n == 0 && (rc = (int)hipMemsetAsync(sets[k].loss_terms_out, 0, (size_t)c.net.nout * sizeof(float), st))) return rc;
-                return PINN_OK;
-            }
+            copy_point_sets(sets, n_sets, d);
+            if (impl->wave_step(c, d, adam_epilogue(params_flat, adam), &rc))      // (empty sets report zeros, as in pinn_data_loss_grad_multi)
+                return rc ? rc : zero_empty_sets(sets, n_sets, c.net.nout, static_cast<hipStream_t>(stream));
         }
     }
     // ---- every other case (other widths / depths, PINN_PREC_FP32, an empty set, a small workspace): the same results from the calls one by one
-    int rc = pinn_wave2d_loss_grad(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, loss_terms_out,
-                                   grad_flat_out, accumulate, precision_mode, workspace, ws_bytes, stream);
+    rc = pinn_wave2d_loss_grad(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, loss_terms_out,
+                               grad_flat_out, accumulate, precision_mode, workspace, ws_bytes, stream);
     if (rc) return rc;
     if (n_sets > 0) {
         const int packed = n > 0 ? PINN_FLAG_WEIGHTS_PACKED : 0;      // (an empty collocation batch packed nothing)
@@ -604,13 +586,7 @@ int pinn_wave2d_step(float* params_flat, const int* layers, int n_layers, const 
                                        ws_bytes, stream);
         if (rc) return rc;
     }
-    if (adam) {
-        NetDesc net;
-        int width = 0;
-        if ((rc = decode_net(layers, n_layers, net, width, 3))) return rc;
-        return pinn_adam_step(params_flat, adam->m, adam->v, grad_flat_out, net.nparams, adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, stream);
-    }
-    return PINN_OK;
+    return adam_tail(params_flat, layers, n_layers, grad_flat_out, adam, stream);
 }
 
 int pinn_wave2d_fields(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
@@ -621,10 +597,7 @@ int pinn_wave2d_fields(const float* params_flat, const int* layers, int n_layers
     int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
     if (rc) return rc;
     if (n > 0 && !fields_out) return PINN_ERR_NULL;
-    c.fields_out = fields_out;
-    if (n == 0) return 0;
-    if (!impl) return fp32_call(c, HEAD_FIELDS, 0, 4);
-    return impl->fields(c);
+    return run_forward(c, impl, fields_out, &Impl::fields, HEAD_FIELDS, 4);
 }
 
 int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
@@ -639,10 +612,7 @@ int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int 
     if (c.net.nout != 7) return PINN_ERR_LAYERS;
     set_hooke(c, E, mu, rho, plane_strain);
     for (int i = 0; i < 7; ++i) c.tw[i] = term_weights[i];
-    c.fields_out = score_out;
-    if (n == 0) return PINN_OK;
-    if (!impl) return fp32_call(c, HEAD_SCORE, 0, 4, 3, false);
-    return impl->wave_score(c);
+    return run_forward(c, impl, score_out, &Impl::wave_score, HEAD_SCORE, 4);
 }
 
 size_t pinn_select_workspace_bytes(int64_t n) { return (n < 0 || n >= (int64_t)1 << 31) ? 0 : select::WS_BYTES; }
@@ -663,10 +633,7 @@ int pinn_net_streams(const float* params_flat, const int* layers, int n_layers, 
     int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
     if (rc) return rc;
     if (n > 0 && !streams_out) return PINN_ERR_NULL;
-    c.fields_out = streams_out;
-    if (n == 0) return 0;
-    if (!impl) return fp32_call(c, HEAD_FIELDS, 0, 5);
-    return impl->streams(c);
+    return run_forward(c, impl, streams_out, &Impl::streams, HEAD_FIELDS, 5);
 }
 
 int pinn_plate2d_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
@@ -679,18 +646,10 @@ int pinn_plate2d_loss_grad(const float* params_flat, const int* layers, int n_la
     if (rc) return rc;
     if ((n > 0 && !frozen_streams) || !term_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
     if (c.net.nout != 5) return PINN_ERR_LAYERS;
-    c.c1 = (float)(E / (1.0 - mu * mu));               // plane stress, PLATE:416-418
-    c.c2 = (float)(E * mu / (1.0 - mu * mu));
-    c.G = (float)(E / (2.0 * (1.0 + mu)));
-    c.rho = (float)rho;
+    set_hooke(c, E, mu, rho, 0);
     for (int i = 0; i < 5; ++i) c.tw[i] = term_weights[i];
     c.aux = frozen_streams;
-    c.loss_out = loss_terms_out;
-    c.grad_out = grad_flat_out;
-    c.accumulate = accumulate;
-    if (n == 0) return empty_batch(c, 5);
-    if (!impl) return fp32_call(c, HEAD_PLATE, 5, 5);
-    return impl->plate_loss_grad(c);
+    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 5, &Impl::plate_loss_grad, HEAD_PLATE, 5);
 }
 
 int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
@@ -703,13 +662,10 @@ int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int
     if (rc) return rc;
     if (!term_weights || (n > 0 && (!frozen_streams || !score_out))) return PINN_ERR_NULL;
     if (c.net.nout != 5) return PINN_ERR_LAYERS;
-    set_hooke(c, E, mu, rho, 0);                       // plane stress, PLATE:416-418: the expressions of pinn_plate2d_loss_grad
+    set_hooke(c, E, mu, rho, 0);
     for (int i = 0; i < 5; ++i) c.tw[i] = term_weights[i];
     c.aux = frozen_streams;
-    c.fields_out = score_out;
-    if (n == 0) return PINN_OK;
-    if (!impl) return fp32_call(c, HEAD_SCORE_PLATE, 0, 5, 3, false);
-    return impl->plate_score(c);
+    return run_forward(c, impl, score_out, &Impl::plate_score, HEAD_SCORE_PLATE, 5);
 }
 
 int pinn_plate2d_traction_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y,
@@ -726,12 +682,7 @@ int pinn_plate2d_traction_loss_grad(const float* params_flat, const int* layers,
     c.tw[0] = weights[0];
     c.tw[1] = weights[1];
     c.aux = frozen_and_normals;
-    c.loss_out = loss_terms_out;
-    c.grad_out = grad_flat_out;
-    c.accumulate = accumulate;
-    if (n == 0) return empty_batch(c, 2);
-    if (!impl) return fp32_call(c, HEAD_TRACTION, 2, 1);
-    return impl->traction_loss_grad(c);
+    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 2, &Impl::traction_loss_grad, HEAD_TRACTION, 1);
 }
 
 int pinn_plate2d_step(float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
@@ -740,20 +691,18 @@ int pinn_plate2d_step(float* params_flat, const int* layers, int n_layers, const
                       const float* hole_frozen_and_normals, const float hole_weights[2], float* hole_loss_terms_out, float* grad_flat_out, int accumulate,
                       const pinn_adam_state* adam, int precision_mode, void* workspace, size_t ws_bytes, void* stream) {
     if (hole_n < 0) return PINN_ERR_SIZE;
-    if (adam && (!adam->m || !adam->v || adam->step < 1)) return adam->step < 1 ? PINN_ERR_SIZE : PINN_ERR_NULL;
+    int rc = check_adam(adam);
+    if (rc) return rc;
     if (hole_n > 0 && (!hole_x || !hole_y || !hole_t || !hole_frozen_and_normals || !hole_weights || !hole_loss_terms_out)) return PINN_ERR_NULL;
     // ---- the one-launch form (fused_step_kernel<..., NSC = 5>): the five-stream collocation set and the hole-traction set
     if (n > 0 && hole_n > 0 && frozen_streams && term_weights && loss_terms_out && grad_flat_out) {
         Call c;
         const Impl* impl = nullptr;
-        int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+        rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
         if (rc) return rc;
         if (c.net.nout != 5) return PINN_ERR_LAYERS;
         if (impl) {
-            c.c1 = (float)(E / (1.0 - mu * mu));               // plane stress, PLATE:416-418
-            c.c2 = (float)(E * mu / (1.0 - mu * mu));
-            c.G = (float)(E / (2.0 * (1.0 + mu)));
-            c.rho = (float)rho;
+            set_hooke(c, E, mu, rho, 0);
             for (int i = 0; i < 5; ++i) c.tw[i] = term_weights[i];
             c.aux = frozen_streams;
             c.loss_out = loss_terms_out;
@@ -771,14 +720,12 @@ int pinn_plate2d_step(float* params_flat, const int* layers, int n_layers, const
             d.loss_out = hole_loss_terms_out;
             d.one_stream_head = 1;
             d.nsets = 0;
-            AdamEpilogue ep = {nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f};
-            if (adam) ep = AdamEpilogue{params_flat, adam->m, adam->v, adam_lr_t(adam->lr, adam->beta1, adam->beta2, adam->step), (float)adam->beta1, (float)adam->beta2, (float)adam->eps};
-            if (impl->plate_step(c, d, ep, &rc)) return rc;
+            if (impl->plate_step(c, d, adam_epilogue(params_flat, adam), &rc)) return rc;
         }
     }
     // ---- every other case: the calls one after the other, the same bits
-    int rc = pinn_plate2d_loss_grad(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, frozen_streams, E, mu, rho, term_weights, loss_terms_out,
-                                    grad_flat_out, accumulate, precision_mode, workspace, ws_bytes, stream);
+    rc = pinn_plate2d_loss_grad(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, frozen_streams, E, mu, rho, term_weights, loss_terms_out,
+                                grad_flat_out, accumulate, precision_mode, workspace, ws_bytes, stream);
     if (rc) return rc;
     if (hole_loss_terms_out && hole_weights) {             // (an empty hole set reports zeros; no hole set at all: NULL outputs)
         const int packed = n > 0 ? PINN_FLAG_WEIGHTS_PACKED : 0;
@@ -786,13 +733,7 @@ int pinn_plate2d_step(float* params_flat, const int* layers, int n_layers, const
                                              hole_weights, hole_loss_terms_out, grad_flat_out, 1, precision_mode | packed, workspace, ws_bytes, stream);
         if (rc) return rc;
     }
-    if (adam) {
-        NetDesc net;
-        int width = 0;
-        if ((rc = decode_net(layers, n_layers, net, width, 3))) return rc;
-        return pinn_adam_step(params_flat, adam->m, adam->v, grad_flat_out, net.nparams, adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, stream);
-    }
-    return PINN_OK;
+    return adam_tail(params_flat, layers, n_layers, grad_flat_out, adam, stream);
 }
 
 int pinn_stream_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
@@ -807,12 +748,7 @@ int pinn_stream_loss_grad(const float* params_flat, const int* layers, int n_lay
     for (int s = 0; s < 5; ++s)
         for (int o = 0; o < c.net.nout; ++o) c.w5[s][o] = weights[s * c.net.nout + o];
     c.aux = targets;
-    c.loss_out = loss_terms_out;
-    c.grad_out = grad_flat_out;
-    c.accumulate = accumulate;
-    if (n == 0) return empty_batch(c, c.net.nout);
-    if (!impl) return fp32_call(c, HEAD_STREAMS, c.net.nout, 5);
-    return impl->stream_loss_grad(c);
+    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, c.net.nout, &Impl::stream_loss_grad, HEAD_STREAMS, 5);
 }
 
 int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int n_layers, const pinn_stream_set* sets, int n_sets,
@@ -828,7 +764,6 @@ int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int
     c.grad_out = grad_flat_out;
     c.accumulate = accumulate;
     c.n_ssets = n_sets;
-    float wmax = 0.0f;
     for (int k = 0; k < n_sets; ++k) {
         const pinn_stream_set& u = sets[k];
         if (u.n < 0) return PINN_ERR_SIZE;
@@ -841,13 +776,10 @@ int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int
         ss.n = (long)u.n;
         ss.loss_out = u.loss_terms_out;
         for (int s = 0; s < 5; ++s)
-            for (int o = 0; o < 8; ++o) {
-                const float w = o < c.net.nout ? u.weights[s][o] : 0.0f;
-                ss.w[s][o] = w;
-                if ((w < 0 ? -w : w) > wmax) wmax = w < 0 ? -w : w;
-            }
+            for (int o = 0; o < 8; ++o) ss.w[s][o] = o < c.net.nout ? u.weights[s][o] : 0.0f;
     }
     if (impl) return impl->stream_sets_loss_grad(c);
+    const float wmax = stream_sets_wmax(c);
     // PINN_PREC_FP32: the sets one after the other, under the call's one normalisation
     bool first = true;
     for (int k = 0; k < n_sets; ++k) {
@@ -856,19 +788,7 @@ int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int
             if ((rc = (int)hipMemsetAsync(ss.loss_out, 0, (size_t)c.net.nout * sizeof(float), c.stream))) return rc;
             continue;
         }
-        Call s = c;
-        s.n_ssets = 0;
-        s.x = ss.x;
-        s.y = ss.y;
-        s.t = ss.t;
-        s.n = ss.n;
-        s.aux = ss.targets;
-        for (int i = 0; i < 5; ++i)
-            for (int o = 0; o < 8; ++o) s.w5[i][o] = ss.w[i][o];
-        s.w5_norm = wmax;
-        s.loss_out = ss.loss_out;
-        s.accumulate = accumulate || !first;
-        if ((rc = fp32_call(s, HEAD_STREAMS, c.net.nout, 5))) return rc;
+        if ((rc = fp32_call(set_call(c, ss, wmax, first), HEAD_STREAMS, c.net.nout, 5))) return rc;
         first = false;
     }
     if (first && !accumulate) return (int)hipMemsetAsync(grad_flat_out, 0, (size_t)c.net.nparams * sizeof(float), c.stream);
@@ -886,14 +806,9 @@ int pinn_nc3d_loss_grad(const float* params_flat, const int* layers, int n_layer
     if (rc) return rc;
     if (!term_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
     if (c.net.nout != 12) return PINN_ERR_LAYERS;
-    hooke3d(c, E, mu, rho);
+    set_hooke(c, E, mu, rho, 1);
     for (int i = 0; i < 12; ++i) c.tw[i] = term_weights[i];
-    c.loss_out = loss_terms_out;
-    c.grad_out = grad_flat_out;
-    c.accumulate = accumulate;
-    if (n == 0) return empty_batch(c, 12);
-    if (!impl) return fp32_call(c, HEAD_NC3D, 12, 5, 4);
-    return impl->nc3d_loss_grad(c);
+    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 12, &Impl::nc3d_loss_grad, HEAD_NC3D, 5, 4);
 }
 
 int pinn_nc3d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
@@ -906,12 +821,9 @@ int pinn_nc3d_residual_score(const float* params_flat, const int* layers, int n_
     if (rc) return rc;
     if (!term_weights || (n > 0 && !score_out)) return PINN_ERR_NULL;
     if (c.net.nout != 12) return PINN_ERR_LAYERS;
-    hooke3d(c, E, mu, rho);
+    set_hooke(c, E, mu, rho, 1);
     for (int i = 0; i < 12; ++i) c.tw[i] = term_weights[i];
-    c.fields_out = score_out;
-    if (n == 0) return PINN_OK;
-    if (!impl) return fp32_call(c, HEAD_SCORE3D, 0, 5, 4, false);
-    return impl->nc3d_score(c);
+    return run_forward(c, impl, score_out, &Impl::nc3d_score, HEAD_SCORE3D, 5, 4);
 }
 
 int pinn_nc3d_data_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
@@ -925,12 +837,7 @@ int pinn_nc3d_data_loss_grad(const float* params_flat, const int* layers, int n_
     if (!out_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
     for (int i = 0; i < c.net.nout; ++i) c.tw[i] = out_weights[i];
     c.targets = targets;
-    c.loss_out = loss_terms_out;
-    c.grad_out = grad_flat_out;
-    c.accumulate = accumulate;
-    if (n == 0) return empty_batch(c, c.net.nout);
-    if (!impl) return fp32_call(c, HEAD_DATA3D, c.net.nout, 1, 4);
-    return impl->nc3d_data_loss_grad(c);
+    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, c.net.nout, &Impl::nc3d_data_loss_grad, HEAD_DATA3D, 1, 4);
 }
 
 int pinn_nc3d_fields(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
@@ -941,21 +848,15 @@ int pinn_nc3d_fields(const float* params_flat, const int* layers, int n_layers, 
     int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
     if (rc) return rc;
     if (n > 0 && !fields_out) return PINN_ERR_NULL;
-    c.fields_out = fields_out;
-    if (n == 0) return 0;
-    if (!impl) return fp32_call(c, HEAD_FIELDS3D, 0, 5, 4);
-    return impl->nc3d_fields(c);
+    return run_forward(c, impl, fields_out, &Impl::nc3d_fields, HEAD_FIELDS3D, 5, 4);
 }
 
 int pinn_adam_step(float* params_flat, float* m, float* v, const float* grad_flat, int64_t n_params, double lr, double beta1,
                    double beta2, double eps, int64_t step, void* stream) {
     if (!params_flat || !m || !v || !grad_flat) return PINN_ERR_NULL;
     if (n_params <= 0 || step < 1) return PINN_ERR_SIZE;
-    // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)   (TF1 AdamOptimizer)
-    const double b1t = __builtin_pow(beta1, (double)step), b2t = __builtin_pow(beta2, (double)step);
-    const double lr_t = lr * __builtin_sqrt(1.0 - b2t) / (1.0 - b1t);
     hipLaunchKernelGGL((adam_tf1_kernel<0>), dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params_flat, m, v,
-                       grad_flat, (long)n_params, (float)lr_t, (float)beta1, (float)beta2, (float)eps);
+                       grad_flat, (long)n_params, adam_lr_t(lr, beta1, beta2, step), (float)beta1, (float)beta2, (float)eps);
     return (int)hipGetLastError();
 }
 

@@ -127,9 +127,55 @@ struct Impl {
     // the same for the plate family (HEAD_SCORE_PLATE, `aux` = frozen streams) and the 4-input family (HEAD_SCORE3D); split modes only
     int (*plate_score)(const Call&);
     int (*nc3d_score)(const Call&);
+    // pinn_debug_cache_policy: the collocation kernel compiled for this net and head (asked of the F16 split-3 line of the net's width)
+    int (*cache_policy)(const NetDesc&, int head, size_t* images_bytes, size_t* sums_bytes);
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// largest |v| of a range of weights (the kernels only ever see a call's weights normalised by it)
+inline float max_abs(const float* v, int n, float m = 0.0f) {
+    for (int i = 0; i < n; ++i) { const float a = v[i] < 0 ? -v[i] : v[i]; if (a > m) m = a; }
+    return m;
+}
+
+// One set of a multi-set call as a call of its own: the two-kernel and fp32 paths run the sets one after the other into the same gradient
+// (`first`: no set of the call ran before this one; a stream-target set keeps the call's one normalisation `wmax`).
+inline Call set_call(const Call& c, const DataSet& s, bool first) {
+    Call r = c;
+    r.nsets = 0;
+    r.x = s.x;
+    r.y = s.y;
+    r.t = s.t;
+    r.n = s.n;
+    r.targets = s.targets;
+    for (int i = 0; i < 8; ++i) r.tw[i] = s.tw[i];
+    r.loss_out = s.loss_out;
+    r.accumulate = c.accumulate || !first;
+    r.weights_packed = c.weights_packed || !first;
+    return r;
+}
+inline float stream_sets_wmax(const Call& c) {      // the one normalisation of a pinn_stream_loss_grad_multi call
+    float m = 0.0f;
+    for (int k = 0; k < c.n_ssets; ++k) m = max_abs(&c.ssets[k].w[0][0], 40, m);
+    return m;
+}
+inline Call set_call(const Call& c, const StreamSet& s, float wmax, bool first) {
+    Call r = c;
+    r.n_ssets = 0;
+    r.x = s.x;
+    r.y = s.y;
+    r.t = s.t;
+    r.n = s.n;
+    r.aux = s.targets;
+    for (int i = 0; i < 5; ++i)
+        for (int o = 0; o < 8; ++o) r.w5[i][o] = s.w[i][o];
+    r.w5_norm = wmax;
+    r.loss_out = s.loss_out;
+    r.accumulate = c.accumulate || !first;
+    r.weights_packed = c.weights_packed || !first;
+    return r;
+}
 
 // pair of HIP events of the optional per-kernel timing, released on every exit path
 struct EventPair {
@@ -163,21 +209,7 @@ struct Host {
     static constexpr int FUSED_MAX_WIDTH = 160;     // widest padded net the fused kernel takes (160: 4 streams, 6 layers = CONF:891; 128: 4 and 1 streams (+ the 3-D head); 96 also 5 streams)
     static constexpr size_t FUSED_ACC_W64 = 32 * 1024;
     static constexpr size_t FUSED_ACC_BYTES = WIDTH <= 64 ? FUSED_ACC_W64 : (WIDTH <= 96 ? 72 * 1024 : 160 * 1024);     // per weight-gradient wave: in-memory accumulator blocks
-    // fused_step_kernel (collocation set + side sets of a training step in one launch): the narrow layouts, and (round 6) every LDS-operand
-    // layout that has both of its parts -- the reference's own nets pay 0.36 ms (8 x 80) / 0.61 ms (8 x 100) of a 6.6 / 10.6 ms step for their
-    // side sets as a second launch (profiles/r06_wide_kernel_stats.csv)
-    static constexpr bool step_has() { return true; }
-    template <int NSC>
-    static constexpr bool step_has_ns() {
-        if (WIDTH <= 64) return NSC == 4 || SPLIT == 3;      // (the plate's five streams: split-precision families)
-        // (padded width 160 keeps the separate calls: CONF's own step -- 185 k collocation + 90 k side points, tools/conf_step_time.py -- measured
-        // 3.34 / 3.32 ms as one launch against 3.30 / 3.29 as two: its side part is eleven rounds of its own, nothing to hide in a tail)
-        return WIDTH < 160 && fused_has<NSC>() && fused_has<1>();
-    }
-    // depth of the fused instantiations of this width (narrow: 4 or 8, by the net)
-    static constexpr int WIDE_NL = WIDTH == 160 ? 6 : 8;
-    template <int NS>
-    static constexpr bool fused_has() { return WIDTH <= 64 || (SPLIT == 3 && ((WIDTH <= 96 && (NS == 4 || NS == 5 || NS == 1)) || (WIDTH <= 128 && (NS == 4 || NS == 1)) || (WIDTH == 160 && (NS == 4 || NS == 1)))); }
+    static constexpr int FUSED_PATH = WIDTH <= 64 ? PINN_PATH_FUSED_REGISTERS : PINN_PATH_FUSED_LDS;
     static constexpr int MAX_BLOCKS = 2048;   // chain kernel grid cap (4 waves per block)
     static constexpr long MIN_TILES = 64;
     static constexpr int MAX_REPACK_BLOCKS = 2048;
@@ -254,6 +286,102 @@ struct Host {
         if (fit < 2) return PINN_ERR_WORKSPACE;
         p.chunk_tiles = fit;
         return PINN_OK;
+    }
+
+    // ---- The fused instantiations (pinn_fused.hpp), said ONCE.  A kernel kind is <NS streams, DIN inputs, HS head selector>: <4> and <5> the
+    // collocation kernels of the wave and plate families, <1> the one-stream kernel of the value-only sets, <5, 4> and <1, 4> the same two of the
+    // 3-D family, <5, 3, 1> the stream-target sets (fused_sets_kernel).  fused_has() is the compile-time half (does this line of
+    // pinn_variants.def carry the kind at all), with_fused() the run-time half (the one Fused<...> compiled for a net).  pinn_path_for, the
+    // image count of a workspace, every fused launch and pinn_debug_cache_policy ask these two; nothing else names a Fused type by its depth.
+    template <int NL_, int NS_, bool FS_ = false, int DIN_ = 3, int HS_ = 0>
+    struct FusedKey {
+        static constexpr int NL = NL_, NS = NS_, DIN = DIN_;
+        static constexpr bool FS = FS_;
+        typedef Fused<Op, SPLIT, WIDTH, NL_, NS_, FS_, DIN_, HS_> F;
+    };
+    template <int NS, int DIN = 3, int HS = 0>
+    static constexpr bool fused_has() {
+        if (HS == 1) return SPLIT == 3 && WIDTH <= 64;      // the reference's 4 x 20 distance / particular nets (PLATE:527-559)
+        if (DIN == 4) return SPLIT == 3 && WIDTH == 128;    // BASELINE configs[4]
+        // padded width <= 64: tile state in registers, every mode; wider: the LDS-operand layouts of the split modes -- four and one stream(s) at
+        // 96, 128 and 160, five at 96 only (PLATE:885 8 x 70)
+        return WIDTH <= 64 || (SPLIT == 3 && (NS != 5 || WIDTH == 96));
+    }
+    // fn(FusedKey<...>()) with the instantiation compiled for this net, and its value; 0 where there is none.  The depths are the ones the
+    // reference's scripts use.  fast_state: the call asks for PINN_FLAG_STATE_FP16, which the collocation kernel of the 8-layer wave nets has.
+    template <int NS, int DIN = 3, int HS = 0, class Fn>
+    static int with_fused(const NetDesc& net, int fast_state, Fn&& fn) {
+        if constexpr (!fused_has<NS, DIN, HS>()) return 0;
+        else if constexpr (HS == 1) return net.nl == 4 ? fn(FusedKey<4, 5, false, 3, 1>()) : 0;
+        else if constexpr (DIN == 4) return net.nl == 10 && net.din == 4 && net.nout == 12 ? fn(FusedKey<10, NS, false, 4>()) : 0;
+        else if constexpr (WIDTH == 160) return net.nl == 6 ? fn(FusedKey<6, NS>()) : 0;      // CONF:891 6 x 140 (other depths of a one-stream layout would not fit the LDS)
+        else if constexpr (WIDTH > 64) return net.nl == 8 ? fn(FusedKey<8, NS>()) : 0;        // INF:645 8 x 80, SEMI:679 8 x 100
+        else {
+            if (net.nl == 4) return fn(FusedKey<4, NS>());
+            if (net.nl != 8) return 0;
+            if (fast_state && SPLIT == 3 && NS == 4) return fn(FusedKey<8, NS, true>());
+            return fn(FusedKey<8, NS>());
+        }
+    }
+    // bytes of one workgroup's scratch images for the kind's kernel of this net; 0: no such kernel.  (Sized for the default layout, which parks
+    // more than the fp16-state one, also where that one is launched.)
+    template <int NS, int DIN = 3, int HS = 0>
+    static size_t image_bytes(const NetDesc& net) {
+        size_t bytes = 0;
+        with_fused<NS, DIN, HS>(net, 0, [&](auto k) { typedef typename decltype(k)::F F; bytes = (size_t)F::TILES * F::SCRATCH_BYTES; return 1; });
+        return bytes;
+    }
+    template <int NS, int DIN = 3, int HS = 0>
+    static bool fused_depth(const NetDesc& net) { return image_bytes<NS, DIN, HS>(net) != 0; }
+    // scratch images (= persistent workgroups) a workspace of ws_bytes holds for it
+    template <int NS, int DIN = 3, int HS = 0>
+    static long fused_images(const NetDesc& net, size_t ws_bytes) {
+        const size_t per_wg = image_bytes<NS, DIN, HS>(net);
+        Plan p;
+        plan_fixed<4>(net, 1, p);
+        return per_wg && ws_bytes > p.fixed_end ? (long)((ws_bytes - p.fixed_end) / per_wg) : 0;
+    }
+    // workgroups of a persistent launch of nsteps steps over that many images; 0: too few for a persistent launch (see FUSED_MIN_GRID) --
+    // the two-kernel path runs
+    static long fused_grid(long images, long nsteps) {
+        long grid = images < FUSED_GRID ? images : FUSED_GRID;
+        if (g_fused_grid_cap > 0 && grid > g_fused_grid_cap) grid = g_fused_grid_cap;
+        if (grid > nsteps) grid = nsteps;
+        return grid < FUSED_MIN_GRID && grid < nsteps ? 0 : grid;
+    }
+    // pinn_path_for: the path a call of this kind takes for this net (ws_bytes == 0: a workspace that holds every scratch image)
+    template <int NS, int DIN = 3, int HS = 0>
+    static int path_of(const NetDesc& net, size_t ws_bytes) {
+        const bool fused = fused_depth<NS, DIN, HS>(net) && (ws_bytes == 0 || fused_images<NS, DIN, HS>(net, ws_bytes) >= FUSED_MIN_GRID);
+        return fused ? FUSED_PATH : PINN_PATH_TWO_KERNEL;
+    }
+    static int path_for(const NetDesc& net, int head, size_t ws_bytes) {
+        if (SPLIT != 3 && head >= PINN_HEAD_PLATE && head <= PINN_HEAD_STREAM_SETS) return PINN_ERR_PRECISION;      // the five-stream and 4-input families
+        switch (head) {
+            case PINN_HEAD_WAVE: return path_of<4>(net, ws_bytes);
+            case PINN_HEAD_DATA: return path_of<1>(net, ws_bytes);
+            case PINN_HEAD_PLATE: return path_of<5>(net, ws_bytes);
+            case PINN_HEAD_NC3D: return path_of<5, 4>(net, ws_bytes);
+            case PINN_HEAD_NC3D_DATA: return path_of<1, 4>(net, ws_bytes);
+            case PINN_HEAD_STREAMS: return PINN_PATH_TWO_KERNEL;
+            case PINN_HEAD_STREAM_SETS: return path_of<5, 3, 1>(net, ws_bytes);
+            default: return PINN_ERR_LAYERS;
+        }
+    }
+    // pinn_debug_cache_policy: the memory classes of the collocation kernel of this net and head, and which of them it marks non-temporal
+    static int cache_policy(const NetDesc& net, int head, size_t* images_bytes, size_t* sums_bytes) {
+        int policy = PINN_ERR_LAYERS;
+        auto ask = [&](auto k) {
+            typedef typename decltype(k)::F F;
+            if (images_bytes) *images_bytes = F::IMAGES_WG_BYTES;
+            if (sums_bytes) *sums_bytes = F::SUMS_WG_BYTES;
+            policy = F::NT_SUMS ? 1 : (F::NT_IMAGES ? 2 : 0);
+            return 1;
+        };
+        if (head == PINN_HEAD_WAVE) with_fused<4>(net, 0, ask);
+        if (head == PINN_HEAD_PLATE) with_fused<5>(net, 0, ask);
+        if (head == PINN_HEAD_NC3D) with_fused<5, 4>(net, 0, ask);
+        return policy;
     }
 
     static PackedWeights packed(const Call& c, const Plan& p) {
@@ -346,17 +474,13 @@ struct Host {
         rc = repack(c, p);
         if (rc) return rc;
         toc(0);
-        float twmax = 0.0f;
-        for (int i = 0; i < 16; ++i) { const float v = c.tw[i] < 0 ? -c.tw[i] : c.tw[i]; if (v > twmax) twmax = v; }
+        float twmax = max_abs(c.tw, 16);
         if (HEAD != HEAD_STREAMS) twmax *= (float)(1u << c.adj_shift);      // the weights are only ever used normalised: folds the shift in
         ChainArgs a;
         fill_common(c, p, a);
         for (int i = 0; i < 16; ++i) a.tw[i] = twmax > 0.0f ? c.tw[i] / twmax : 0.0f;
         if (HEAD == HEAD_STREAMS) {
-            twmax = 0.0f;
-            for (int i = 0; i < 5; ++i)
-                for (int o = 0; o < 8; ++o) { const float v = c.w5[i][o] < 0 ? -c.w5[i][o] : c.w5[i][o]; if (v > twmax) twmax = v; }
-            if (c.w5_norm > 0.0f) twmax = c.w5_norm;
+            twmax = c.w5_norm > 0.0f ? c.w5_norm : max_abs(&c.w5[0][0], 40);
             for (int i = 0; i < 5; ++i)
                 for (int o = 0; o < 8; ++o) a.w5[i][o] = twmax > 0.0f ? c.w5[i][o] / twmax : 0.0f;
         }
@@ -402,7 +526,6 @@ struct Host {
         return rc;
     }
 
-    // fused path (pinn_fused.hpp): padded width <= 64 and a compiled depth; needs the per-wave state scratch in the workspace
     // The value-only sets of a call as a table (a single-set call becomes a table of one).
     static int data_sets(const Call& c, DataSet (&sets)[4]) {
         if (c.nsets > 0) {
@@ -424,38 +547,52 @@ struct Host {
         return 1;
     }
 
-    // the 3-D instantiation (4 inputs, five first-order streams, 10 x 128: BASELINE configs[4]) exists for the split-precision width-128 family
-    static constexpr bool fused_has_3d() { return SPLIT == 3 && WIDTH == 128; }
-    // Arguments of one part of a fused launch: `area` 0 = the call's own per-workgroup areas, 1 = the second set (the side-set part of
-    // fused_step_kernel); `scratch_off` = byte offset of this part's scratch images behind p.panels; `block0` = its first workgroup.
+    // What every part of a fused launch is given: the net and its weights in the fused format, the input map, the part's areas in the workspace
+    // and its place in the launch.  `area` 0 = the call's own per-workgroup areas, 1 = the second set (the side-set part of fused_step_kernel);
+    // `scratch_off` = byte offset of this part's scratch images behind p.panels; `block0` = its first workgroup.  Everything else is zero: no
+    // points, no sets, no constants, no XCD tail -- the caller fills in what its kernel reads.
+    static void fused_args(const Call& c, const Plan& p, int grid, long nsteps, int area, size_t scratch_off, int block0, FusedArgs& a) {
+        char* b = static_cast<char*>(c.ws);
+        a = FusedArgs{};
+        a.net = c.net;
+        a.pw = packed(c, p);
+        a.pw.frags = reinterpret_cast<const u32x4*>(b + p.frags_fused);
+        a.frags_bytes = (unsigned)((size_t)FI::total(c.net.nl) * FUSED_PARTS * 64 * sizeof(u32x4));
+        a.nsteps = nsteps;
+        for (int k = 0; k < 4; ++k) { a.sx[k] = c.sx[k]; a.ox[k] = c.ox[k]; }
+        a.scratch = reinterpret_cast<u32x4*>(b + p.panels + scratch_off);
+        a.loss_part = reinterpret_cast<float*>(b + (area ? p.loss_part_b : p.loss_part));
+        a.partial = reinterpret_cast<float*>(b + (area ? p.partial_b : p.partial));
+        a.wg_acc = reinterpret_cast<u32x4*>(b + (area ? p.wg_acc_b : p.wg_acc));
+        a.block0 = block0;
+        a.grid = grid;
+        a.n_plain = 0x7fffffffffffffffL;
+    }
     struct FusedSetup {
         FusedArgs a;
         float twmax;
         LossOuts lo;
         int nsets;
     };
-    template <int NL, int NS, bool FS = false, int DIN = 3>
+    // one part of a launch of fused_wave_kernel / fused_step_kernel for the instantiation K (a FusedKey)
+    template <class K>
     static void fused_setup(const Call& c, const Plan& p, int grid, long nsteps, int area, size_t scratch_off, int block0, FusedSetup& su) {
-        typedef Fused<Op, SPLIT, WIDTH, NL, NS, FS, DIN> F;
-        char* b = static_cast<char*>(c.ws);
+        typedef typename K::F F;
+        constexpr int NS = K::NS, DIN = K::DIN;
+        static_assert(F::WG_ACC_BYTES <= FUSED_ACC_BYTES, "accumulator area of the plan");
         FusedArgs& a = su.a;
-        a.net = c.net;
-        a.pw = packed(c, p);
-        a.pw.frags = reinterpret_cast<const u32x4*>(b + p.frags_fused);
-        a.frags_bytes = (unsigned)((size_t)FI::total(c.net.nl) * FUSED_PARTS * 64 * sizeof(u32x4));
+        fused_args(c, p, grid, nsteps, area, scratch_off, block0, a);
         a.x = c.x;
         a.y = c.y;
         a.t = c.t;
         a.z = c.z;
         a.n = c.n;
-        a.nsteps = nsteps;
-        for (int k = 0; k < 4; ++k) { a.sx[k] = c.sx[k]; a.ox[k] = c.ox[k]; }
         a.c1 = c.c1;
         a.c2 = c.c2;
         a.G = c.G;
         a.rho = c.rho;
-        a.targets = nullptr;
         a.aux = c.aux;
+        a.dbg = c.dbg_stamps;
         float twmax = 0.0f;
         LossOuts lo = {{nullptr, nullptr, nullptr, nullptr}};
         int nsets = 1;
@@ -463,48 +600,36 @@ struct Host {
             DataSet sets[4];
             nsets = data_sets(c, sets);
             constexpr int NTW = DIN == 4 ? 16 : 8;      // output weights of a set
-            for (int k = 0; k < nsets; ++k)
-                for (int i = 0; i < NTW; ++i) { const float v = sets[k].tw[i] < 0 ? -sets[k].tw[i] : sets[k].tw[i]; if (v > twmax) twmax = v; }
+            for (int k = 0; k < nsets; ++k) twmax = max_abs(sets[k].tw, NTW, twmax);
             twmax *= (float)(1u << c.adj_shift);
             if constexpr (F::WG_HI) twmax *= 1.0f / F::ZDB_SEED_SCALE;
             long s0 = 0;
-            for (int k = 0; k < 4; ++k) {
-                const bool on = k < nsets;
+            for (int k = 0; k < nsets; ++k) {
                 a.set_step0[k] = s0;
-                a.set_x[k] = on ? sets[k].x : nullptr;
-                a.set_y[k] = on ? sets[k].y : nullptr;
-                a.set_t[k] = on ? sets[k].t : nullptr;
-                a.set_z[k] = on ? sets[k].z : nullptr;
-                a.set_targets[k] = on ? sets[k].targets : nullptr;
-                a.set_n[k] = on ? sets[k].n : 0;
-                a.set_head[k] = on ? sets[k].head : 0;
-                a.set_aux[k] = on ? sets[k].aux : nullptr;
-                for (int i = 0; i < 16; ++i) a.set_tw[k][i] = on && i < NTW && twmax > 0.0f ? sets[k].tw[i] / twmax : 0.0f;
-                if (on) { s0 += (sets[k].n + 16 * F::TILES - 1) / (16 * F::TILES); lo.p[k] = sets[k].loss_out; }
+                a.set_x[k] = sets[k].x;
+                a.set_y[k] = sets[k].y;
+                a.set_t[k] = sets[k].t;
+                a.set_z[k] = sets[k].z;
+                a.set_targets[k] = sets[k].targets;
+                a.set_n[k] = sets[k].n;
+                a.set_head[k] = sets[k].head;
+                a.set_aux[k] = sets[k].aux;
+                for (int i = 0; i < NTW; ++i) a.set_tw[k][i] = twmax > 0.0f ? sets[k].tw[i] / twmax : 0.0f;
+                s0 += (sets[k].n + 16 * F::TILES - 1) / (16 * F::TILES);
+                lo.p[k] = sets[k].loss_out;
             }
-            a.set_step0[4] = s0;
+            for (int k = nsets; k <= 4; ++k) a.set_step0[k] = s0;
             a.nsets = nsets;
-            for (int i = 0; i < 16; ++i) a.tw[i] = 0.0f;
         } else {
-            for (int i = 0; i < 16; ++i) { const float v = c.tw[i] < 0 ? -c.tw[i] : c.tw[i]; if (v > twmax) twmax = v; }
-            twmax *= (float)(1u << c.adj_shift);
+            twmax = max_abs(c.tw, 16) * (float)(1u << c.adj_shift);
             if constexpr (F::WG_HI) twmax *= 1.0f / F::ZDB_SEED_SCALE;      // adjoint seeds x 16: the weight gradient's fp16 adjoints in the normal range (Fused::ZDB)
             for (int i = 0; i < 16; ++i) a.tw[i] = twmax > 0.0f ? c.tw[i] / twmax : 0.0f;
             a.nsets = 1;
             lo.p[0] = c.loss_out;
         }
-        a.scratch = reinterpret_cast<u32x4*>(b + p.panels + scratch_off);
-        a.loss_part = reinterpret_cast<float*>(b + (area ? p.loss_part_b : p.loss_part));
-        a.partial = reinterpret_cast<float*>(b + (area ? p.partial_b : p.partial));
-        a.wg_acc = reinterpret_cast<u32x4*>(b + (area ? p.wg_acc_b : p.wg_acc));
-        static_assert(F::WG_ACC_BYTES <= FUSED_ACC_BYTES, "accumulator area of the plan");
-        a.dbg = c.dbg_stamps;
-        a.block0 = block0;
-        a.grid = grid;
         // XCD-aware step assignment (FusedArgs::n_plain): the collocation part of a full grid with enough rounds for the skew to be expressible in
         // whole steps: g_xcd_tail_permille / 1000 more steps for the even-XCD workgroups, taken as a tail behind R plain rounds with
         // 128 (R + e) + 128 R = nsteps, e = skew * R; not the side-set part (its workgroups start wherever a compute unit frees up)
-        a.n_plain = 0x7fffffffffffffffL;
 #if defined(PINN_SIMT_EMULATOR)
         const bool shape_ok = grid >= 8 && grid % 8 == 0 && nsteps >= 4L * grid;      // (the x86 test build: small grids, a few rounds -- the index arithmetic is the point)
 #else
@@ -519,124 +644,119 @@ struct Host {
         su.nsets = nsets;
     }
 
-    template <int NL, int NS, bool FS = false, int DIN = 3>
+    template <class K>
     static int fused_launch(const Call& c, const Plan& p, int grid, int nterms, long nsteps) {
-        if constexpr (DIN == 4 ? fused_has_3d() : fused_has<NS>()) {
-            typedef Fused<Op, SPLIT, WIDTH, NL, NS, FS, DIN> F;
-            int rc = repack(c, p);
-            if (rc) return rc;
-            char* b = static_cast<char*>(c.ws);
-            FusedSetup su;
-            fused_setup<NL, NS, FS, DIN>(c, p, grid, nsteps, 0, 0, 0, su);
-            const FusedArgs& a = su.a;
-            const float twmax = su.twmax;
-            const LossOuts lo = su.lo;
-            const int nsets = su.nsets;
-            EventPair evp(c.prof_ms != nullptr);
-            hipEvent_t (&ev)[2] = evp.ev;
-            if (c.prof_ms) hipEventRecord(ev[0], c.stream);
-            const int ring_slot = c.ring ? c.ring->begin(c.stream, NS) : -1;
-            hipLaunchKernelGGL((fused_wave_kernel<Op, SPLIT, WIDTH, NL, NS, FS, DIN>), dim3(grid), dim3(512), 0, c.stream, a);
-            if (c.ring) c.ring->end(ring_slot, c.stream);
-            if ((rc = (int)hipGetLastError())) return rc;
-            if (c.prof_ms) {
-                hipEventRecord(ev[1], c.stream);
-                hipEventSynchronize(ev[1]);
-                c.prof_ms[0] = c.prof_ms[2] = c.prof_ms[3] = 0.f;
-                hipEventElapsedTime(&c.prof_ms[1], ev[0], ev[1]);
-            }
-            // loss partials are [wave][set][8] with set = FUSED_MAX_SETS slots for NS = 1 and one slot for NS = 4
-            constexpr int SLOTS = NS == 1 ? FUSED_MAX_SETS : 1;
-            if constexpr (DIN == 4) {
-                // 12 terms in LOSS_SLOTS_3D slots per tile: the gradient blocks of the fused reduction, then the loss reduction of the two-kernel path
-                hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), dim3((c.net.nparams + 63) / 64), dim3(256), 0, c.stream, (const float*)a.partial,
-                                   grid, c.net.nparams, twmax, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, 0, 0, SLOTS, lo,
-                                   (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);
-                hipLaunchKernelGGL((reduce_loss_kernel<0>), dim3(1), dim3(256), 0, c.stream, (const float*)a.loss_part, (long)grid * F::TILES, nterms,
-                                   c.loss_out, 0, LOSS_SLOTS_3D * SLOTS, (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);      // (NS = 1: set 0's slots of [tile][FUSED_MAX_SETS][16])
-                return (int)hipGetLastError();
-            }
-            hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), dim3((c.net.nparams + 63) / 64 + nsets), dim3(256), 0, c.stream, (const float*)a.partial,
-                               grid, c.net.nparams, twmax, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, nterms, nsets,
-                               SLOTS, lo, (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);
-            return (int)hipGetLastError();
-        } else {
-            return PINN_ERR_LAYERS;
+        typedef typename K::F F;
+        constexpr int NS = K::NS, DIN = K::DIN;
+        int rc = repack(c, p);
+        if (rc) return rc;
+        char* b = static_cast<char*>(c.ws);
+        FusedSetup su;
+        fused_setup<K>(c, p, grid, nsteps, 0, 0, 0, su);
+        const FusedArgs& a = su.a;
+        const float twmax = su.twmax;
+        const LossOuts lo = su.lo;
+        const int nsets = su.nsets;
+        EventPair evp(c.prof_ms != nullptr);
+        hipEvent_t (&ev)[2] = evp.ev;
+        if (c.prof_ms) hipEventRecord(ev[0], c.stream);
+        const int ring_slot = c.ring ? c.ring->begin(c.stream, NS) : -1;
+        hipLaunchKernelGGL((fused_wave_kernel<Op, SPLIT, WIDTH, K::NL, NS, K::FS, DIN>), dim3(grid), dim3(512), 0, c.stream, a);
+        if (c.ring) c.ring->end(ring_slot, c.stream);
+        if ((rc = (int)hipGetLastError())) return rc;
+        if (c.prof_ms) {
+            hipEventRecord(ev[1], c.stream);
+            hipEventSynchronize(ev[1]);
+            c.prof_ms[0] = c.prof_ms[2] = c.prof_ms[3] = 0.f;
+            hipEventElapsedTime(&c.prof_ms[1], ev[0], ev[1]);
         }
+        // loss partials are [wave][set][8] with set = FUSED_MAX_SETS slots for NS = 1 and one slot for NS = 4
+        constexpr int SLOTS = NS == 1 ? FUSED_MAX_SETS : 1;
+        if constexpr (DIN == 4) {
+            // 12 terms in LOSS_SLOTS_3D slots per tile: the gradient blocks of the fused reduction, then the loss reduction of the two-kernel path
+            hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), dim3((c.net.nparams + 63) / 64), dim3(256), 0, c.stream, (const float*)a.partial,
+                               grid, c.net.nparams, twmax, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, 0, 0, SLOTS, lo,
+                               (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);
+            hipLaunchKernelGGL((reduce_loss_kernel<0>), dim3(1), dim3(256), 0, c.stream, (const float*)a.loss_part, (long)grid * F::TILES, nterms,
+                               c.loss_out, 0, LOSS_SLOTS_3D * SLOTS, (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);      // (NS = 1: set 0's slots of [tile][FUSED_MAX_SETS][16])
+            return (int)hipGetLastError();
+        }
+        hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), dim3((c.net.nparams + 63) / 64 + nsets), dim3(256), 0, c.stream, (const float*)a.partial,
+                           grid, c.net.nparams, twmax, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, nterms, nsets,
+                           SLOTS, lo, (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);
+        return (int)hipGetLastError();
     }
 
     // One training step's sets in one launch + one reduction (+ Adam): fused_step_kernel, reduce_step_kernel.  c = the collocation call
     // (pinn_wave2d_loss_grad's arguments), d = the side sets (pinn_data_loss_grad_multi's; d.nsets > 0).  Returns 1 if it ran (rc in *out), 0 if
     // this net / workspace / set sizes do not take it -- the caller then makes the two calls (+ pinn_adam_step) one after the other: same bits.
-    template <int NL, int NSC, bool FS>
+    // K4 = the collocation part's instantiation, K1 = the side part's: the one-stream kernel of the same depth, default layout.
+    template <class K4, class K1>
     static int step_launch(const Call& c, const Call& d, const AdamEpilogue& adam, const Plan& p, int grid4, long nsteps4, int grid1, long nsteps1, size_t off1,
                            int nterms_a, int nterms_b) {
-        typedef Fused<Op, SPLIT, WIDTH, NL, NSC, FS, 3> F4;
-        typedef Fused<Op, SPLIT, WIDTH, NL, 1, false, 3> F1;
         int rc = repack(c, p);
         if (rc) return rc;
         char* b = static_cast<char*>(c.ws);
         FusedSetup s4, s1;
-        fused_setup<NL, NSC, FS, 3>(c, p, grid4, nsteps4, 0, 0, 0, s4);
-        fused_setup<NL, 1, false, 3>(d, p, grid1, nsteps1, 1, off1, grid4, s1);
-        const int ring_slot = c.ring ? c.ring->begin(c.stream, NSC) : -1;
-        hipLaunchKernelGGL((fused_step_kernel<Op, SPLIT, WIDTH, NL, NSC, FS>), dim3(grid4 + grid1), dim3(512), 0, c.stream, s4.a, s1.a);
+        fused_setup<K4>(c, p, grid4, nsteps4, 0, 0, 0, s4);
+        fused_setup<K1>(d, p, grid1, nsteps1, 1, off1, grid4, s1);
+        const int ring_slot = c.ring ? c.ring->begin(c.stream, K4::NS) : -1;
+        hipLaunchKernelGGL((fused_step_kernel<Op, SPLIT, WIDTH, K4::NL, K4::NS, K4::FS>), dim3(grid4 + grid1), dim3(512), 0, c.stream, s4.a, s1.a);
         if (c.ring) c.ring->end(ring_slot, c.stream);
         if ((rc = (int)hipGetLastError())) return rc;
-        StepPart A = {(const float*)s4.a.partial, grid4, s4.twmax, (const float*)s4.a.loss_part, (long)grid4 * F4::TILES};
-        StepPart B = {(const float*)s1.a.partial, grid1, s1.twmax, (const float*)s1.a.loss_part, (long)grid1 * F1::TILES};
+        StepPart A = {(const float*)s4.a.partial, grid4, s4.twmax, (const float*)s4.a.loss_part, (long)grid4 * K4::F::TILES};
+        StepPart B = {(const float*)s1.a.partial, grid1, s1.twmax, (const float*)s1.a.loss_part, (long)grid1 * K1::F::TILES};
         hipLaunchKernelGGL((reduce_step_kernel<0>), dim3((c.net.nparams + 63) / 64 + s1.nsets + 1), dim3(256), 0, c.stream, A, B, c.net.nparams, c.grad_out,
                            c.accumulate, nterms_a, c.loss_out, nterms_b, s1.nsets, (int)FUSED_MAX_SETS, s1.lo, adam, (const int*)(b + p.wflags),
                            SPLIT == 3 ? repack_blocks(c.net) : 0);
         return (int)hipGetLastError();
     }
+    // fused_step_kernel: the narrow layouts, and (round 6) every LDS-operand layout that has both of its parts -- the reference's own nets pay
+    // 0.36 ms (8 x 80) / 0.61 ms (8 x 100) of a 6.6 / 10.6 ms step for their side sets as a second launch (profiles/r06_wide_kernel_stats.csv)
+    template <int NSC>
+    static constexpr bool step_has() {
+        if (WIDTH <= 64) return NSC == 4 || SPLIT == 3;      // (the plate's five streams: split-precision families)
+        // (padded width 160 keeps the separate calls: CONF's own step -- 185 k collocation + 90 k side points, tools/conf_step_time.py -- measured
+        // 3.34 / 3.32 ms as one launch against 3.30 / 3.29 as two: its side part is eleven rounds of its own, nothing to hide in a tail)
+        return WIDTH < 160 && fused_has<NSC>() && fused_has<1>();
+    }
     // NSC = 4: the wave step (c: pinn_wave2d_loss_grad's call, d: the value-only sets, nterms 7 / n_out); NSC = 5: the plate's (c: pinn_plate2d_loss_grad's
-    // call, d: the hole-traction set as a one-set call with one_stream_head = 1, nterms 5 / 2)
+    // call, d: the hole-traction set as a one-set call with one_stream_head = 1, nterms 5 / 2).  Unlike a single launch it needs room for
+    // all images of both parts or declines, and takes no grid cap.
     template <int NSC>
     static int step(const Call& c, const Call& d, const AdamEpilogue& adam, int* out, int nterms_a, int nterms_b) {
-        if constexpr (step_has_ns<NSC>()) {
-            if (!c.use_fused || c.prof_ms != nullptr || !fused_depth<NSC>(c.net) || !fused_depth<1>(c.net)) return 0;
-            if (((uintptr_t)c.ws & 255) != 0 || c.n <= 0) return 0;
-            Plan p;
-            plan_fixed<4>(c.net, c.n, p);
-            constexpr int T4 = Fused<Op, SPLIT, WIDTH, WIDE_NL, NSC>::TILES, T1 = Fused<Op, SPLIT, WIDTH, WIDE_NL, 1>::TILES;
-            size_t per4, per1;
-            if constexpr (WIDTH > 64) {
-                per4 = (size_t)T4 * Fused<Op, SPLIT, WIDTH, WIDE_NL, NSC>::SCRATCH_BYTES;
-                per1 = (size_t)T1 * Fused<Op, SPLIT, WIDTH, WIDE_NL, 1>::SCRATCH_BYTES;
-            } else {
-                per4 = (size_t)T4 * (c.net.nl == 4 ? Fused<Op, SPLIT, WIDTH, 4, NSC>::SCRATCH_BYTES : Fused<Op, SPLIT, WIDTH, 8, NSC>::SCRATCH_BYTES);
-                per1 = (size_t)T1 * (c.net.nl == 4 ? Fused<Op, SPLIT, WIDTH, 4, 1>::SCRATCH_BYTES : Fused<Op, SPLIT, WIDTH, 8, 1>::SCRATCH_BYTES);
-            }
-            const long nsteps4 = (c.n + 16 * T4 - 1) / (16 * T4);
-            long nsteps1 = 0;
-            DataSet sets[4];
-            const int m = data_sets(d, sets);
-            for (int k = 0; k < m; ++k) nsteps1 += (sets[k].n + 16 * T1 - 1) / (16 * T1);
-            if (nsteps1 == 0) return 0;
-            const long grid4 = nsteps4 < FUSED_GRID ? nsteps4 : FUSED_GRID, grid1 = nsteps1 < FUSED_GRID ? nsteps1 : FUSED_GRID;
-            const size_t off1 = align_up((size_t)grid4 * per4, 256);
-            // the side-set part's own partial sums, behind its scratch images: [loss partials | gradient partials | in-memory weight-gradient sums]
-            size_t bo = align_up(p.fixed_end + off1 + (size_t)grid1 * per1, 256);
-            p.loss_part_b = bo;
-            bo = align_up(bo + (size_t)grid1 * 4 * FUSED_MAX_SETS * 8 * sizeof(float), 256);
-            p.partial_b = bo;
-            bo = align_up(bo + (size_t)grid1 * c.net.nparams * sizeof(float), 256);
-            p.wg_acc_b = bo;
-            bo = align_up(bo + (size_t)grid1 * 4 * FUSED_ACC_BYTES, 256);
-            if (c.ws_bytes < bo) return 0;      // (the two calls then size their grids to the workspace one by one)
-            if constexpr (WIDTH > 64) {
-                *out = step_launch<WIDE_NL, NSC, false>(c, d, adam, p, (int)grid4, nsteps4, (int)grid1, nsteps1, off1, nterms_a, nterms_b);
-                g_path_counts[PINN_PATH_FUSED_LDS] += 2;
+        if constexpr (step_has<NSC>()) {
+            if (!c.use_fused || c.prof_ms != nullptr || ((uintptr_t)c.ws & 255) != 0 || c.n <= 0) return 0;
+            return with_fused<NSC>(c.net, c.fast_state, [&](auto k) {
+                // (the fp16-state layout: the four-stream collocation part only)
+                typedef FusedKey<decltype(k)::NL, NSC, decltype(k)::FS && NSC == 4> K4;
+                typedef FusedKey<K4::NL, 1> K1;
+                constexpr int T4 = K4::F::TILES, T1 = K1::F::TILES;
+                const size_t per4 = image_bytes<NSC>(c.net), per1 = image_bytes<1>(c.net);
+                if (per1 == 0) return 0;
+                Plan p;
+                plan_fixed<4>(c.net, c.n, p);
+                const long nsteps4 = (c.n + 16 * T4 - 1) / (16 * T4);
+                long nsteps1 = 0;
+                DataSet sets[4];
+                const int m = data_sets(d, sets);
+                for (int i = 0; i < m; ++i) nsteps1 += (sets[i].n + 16 * T1 - 1) / (16 * T1);
+                if (nsteps1 == 0) return 0;
+                const long grid4 = nsteps4 < FUSED_GRID ? nsteps4 : FUSED_GRID, grid1 = nsteps1 < FUSED_GRID ? nsteps1 : FUSED_GRID;
+                const size_t off1 = align_up((size_t)grid4 * per4, 256);
+                // the side-set part's own partial sums, behind its scratch images: [loss partials | gradient partials | in-memory weight-gradient sums]
+                size_t bo = align_up(p.fixed_end + off1 + (size_t)grid1 * per1, 256);
+                p.loss_part_b = bo;
+                bo = align_up(bo + (size_t)grid1 * 4 * FUSED_MAX_SETS * 8 * sizeof(float), 256);
+                p.partial_b = bo;
+                bo = align_up(bo + (size_t)grid1 * c.net.nparams * sizeof(float), 256);
+                p.wg_acc_b = bo;
+                bo = align_up(bo + (size_t)grid1 * 4 * FUSED_ACC_BYTES, 256);
+                if (c.ws_bytes < bo) return 0;      // (the two calls then size their grids to the workspace one by one)
+                *out = step_launch<K4, K1>(c, d, adam, p, (int)grid4, nsteps4, (int)grid1, nsteps1, off1, nterms_a, nterms_b);
+                g_path_counts[FUSED_PATH] += 2;      // (both families of the step)
                 return 1;
-            } else {
-            if (NSC == 4 && c.fast_state && SPLIT == 3 && c.net.nl == 8)
-                *out = step_launch<8, NSC, NSC == 4>(c, d, adam, p, (int)grid4, nsteps4, (int)grid1, nsteps1, off1, nterms_a, nterms_b);
-            else *out = c.net.nl == 4 ? step_launch<4, NSC, false>(c, d, adam, p, (int)grid4, nsteps4, (int)grid1, nsteps1, off1, nterms_a, nterms_b)
-                                      : step_launch<8, NSC, false>(c, d, adam, p, (int)grid4, nsteps4, (int)grid1, nsteps1, off1, nterms_a, nterms_b);
-            g_path_counts[PINN_PATH_FUSED_REGISTERS] += 2;      // (both families of the step)
-            return 1;
-            }
+            });
         } else {
             return 0;
         }
@@ -644,130 +764,26 @@ struct Host {
     static int wave_step(const Call& c, const Call& d, const AdamEpilogue& adam, int* out) { return step<4>(c, d, adam, out, 7, c.net.nout); }
     static int plate_step(const Call& c, const Call& d, const AdamEpilogue& adam, int* out) { return step<5>(c, d, adam, out, 5, 2); }
 
-    // The depths the fused kernel is compiled for (the ones the reference's scripts use): the rule of try_fused AND of pinn_path_for.
-    template <int NS>
-    static bool fused_depth(const NetDesc& net) {
-        if constexpr (!fused_has<NS>()) return false;
-        if constexpr (WIDTH == 160) return net.nl == 6;          // padded width 160: the reference's confined-domain net, 6 x 140 (CONF:891)
-        if (net.nl != 4 && net.nl != 8) return false;
-        if (WIDTH > 64 && net.nl != 8) return false;            // padded widths 96 / 128: the 8-layer instantiations only (INF:645 8 x 80, SEMI:679 8 x 100)
-        return true;
-    }
-    // scratch images (= persistent workgroups) a workspace of ws_bytes holds for the NS-stream fused kernel of this net
-    template <int NS>
-    static long fused_images(const NetDesc& net, size_t ws_bytes) {
-        if constexpr (fused_has<NS>()) {
-            Plan p;
-            plan_fixed<4>(net, 1, p);
-            constexpr int TILES = Fused<Op, SPLIT, WIDTH, WIDTH == 160 ? 6 : 4, NS>::TILES;
-            // (sized for the default layout, which parks more than the fp16-state one)
-            size_t per_wg;
-            if constexpr (WIDTH == 160) per_wg = (size_t)TILES * Fused<Op, SPLIT, WIDTH, 6, NS>::SCRATCH_BYTES;      // (one depth: other depths of a one-stream layout would not fit the LDS)
-            else per_wg = (size_t)TILES * (net.nl == 4 ? Fused<Op, SPLIT, WIDTH, 4, NS>::SCRATCH_BYTES : Fused<Op, SPLIT, WIDTH, 8, NS>::SCRATCH_BYTES);
-            if (ws_bytes < p.fixed_end + per_wg) return 0;
-            return (long)((ws_bytes - p.fixed_end) / per_wg);
-        } else {
-            return 0;
-        }
-    }
-    template <int NS = 5>
-    static long fused_images_3d(const NetDesc& net, size_t ws_bytes) {
-        if constexpr (fused_has_3d()) {
-            typedef Fused<Op, SPLIT, WIDTH, 10, NS, false, 4> F;
-            Plan p;
-            plan_fixed<4>(net, 1, p);
-            const size_t per_wg = (size_t)F::TILES * F::SCRATCH_BYTES;
-            if (ws_bytes < p.fixed_end + per_wg) return 0;
-            return (long)((ws_bytes - p.fixed_end) / per_wg);
-        } else {
-            return 0;
-        }
-    }
-    // pinn_path_for: the path a call of this family takes for this net (ws_bytes == 0: a workspace that holds every scratch image)
-    static int path_for(const NetDesc& net, int head, size_t ws_bytes) {
-        const int fused_kind = WIDTH <= 64 ? PINN_PATH_FUSED_REGISTERS : PINN_PATH_FUSED_LDS;
-        auto enough = [&](long images) { return ws_bytes == 0 || images >= FUSED_MIN_GRID; };
-        switch (head) {
-            case PINN_HEAD_WAVE: return fused_depth<4>(net) && enough(fused_images<4>(net, ws_bytes)) ? fused_kind : PINN_PATH_TWO_KERNEL;
-            case PINN_HEAD_DATA: return fused_depth<1>(net) && enough(fused_images<1>(net, ws_bytes)) ? fused_kind : PINN_PATH_TWO_KERNEL;
-            case PINN_HEAD_PLATE:
-                if (SPLIT != 3) return PINN_ERR_PRECISION;
-                return fused_depth<5>(net) && enough(fused_images<5>(net, ws_bytes)) ? fused_kind : PINN_PATH_TWO_KERNEL;
-            case PINN_HEAD_NC3D:
-                if (SPLIT != 3) return PINN_ERR_PRECISION;
-                return fused_has_3d() && net.nl == 10 && net.din == 4 && net.nout == 12 && enough(fused_images_3d(net, ws_bytes)) ? PINN_PATH_FUSED_LDS : PINN_PATH_TWO_KERNEL;
-            case PINN_HEAD_NC3D_DATA:
-                if (SPLIT != 3) return PINN_ERR_PRECISION;
-                return fused_has_3d() && net.nl == 10 && net.din == 4 && net.nout == 12 && enough(fused_images_3d<1>(net, ws_bytes)) ? PINN_PATH_FUSED_LDS : PINN_PATH_TWO_KERNEL;
-            case PINN_HEAD_STREAMS: return SPLIT == 3 ? PINN_PATH_TWO_KERNEL : PINN_ERR_PRECISION;
-            case PINN_HEAD_STREAM_SETS:
-                if (SPLIT != 3) return PINN_ERR_PRECISION;
-                return sets_has() && net.nl == 4 && enough(sets_images(net, ws_bytes)) ? PINN_PATH_FUSED_REGISTERS : PINN_PATH_TWO_KERNEL;
-            default: return PINN_ERR_LAYERS;
-        }
-    }
-
-    // returns 1 if the fused path ran (rc in *out), 0 if it does not apply
-    template <int NS>
+    // One fused launch for a call of kind <NS, DIN>: returns 1 if it ran (rc in *out), 0 if it does not apply -- no instantiation for this net, or
+    // a workspace with too few scratch images -- and the two-kernel path runs.
+    template <int NS, int DIN = 3>
     static int try_fused(const Call& c, int* out, int nterms) {
-        if constexpr (fused_has<NS>()) {
-            if (!fused_depth<NS>(c.net)) return 0;
-            Plan p;
-            if (((uintptr_t)c.ws & 255) != 0) return 0;
-            plan_fixed<4>(c.net, c.n, p);
-            constexpr int TILES = Fused<Op, SPLIT, WIDTH, WIDTH == 160 ? 6 : 4, NS>::TILES;
-            long grid = fused_images<NS>(c.net, c.ws_bytes);
-            if (grid == 0) return 0;
-            if (grid > FUSED_GRID) grid = FUSED_GRID;
-            if (g_fused_grid_cap > 0 && grid > g_fused_grid_cap) grid = g_fused_grid_cap;
+        if (((uintptr_t)c.ws & 255) != 0) return 0;
+        return with_fused<NS, DIN>(c.net, c.fast_state, [&](auto k) {
+            constexpr int TILES = decltype(k)::F::TILES;
             long nsteps = 0;
-            if (NS == 1) {
-                DataSet sets[4];
-                const int m = data_sets(c, sets);
-                for (int k = 0; k < m; ++k) nsteps += (sets[k].n + 16 * TILES - 1) / (16 * TILES);
-            } else {
-                nsteps = (c.n + 16 * TILES - 1) / (16 * TILES);
-            }
-            if (nsteps == 0) return 0;
-            if (grid > nsteps) grid = nsteps;
-            if (grid < FUSED_MIN_GRID && grid < nsteps) return 0;      // too few scratch images for a persistent launch: two-kernel path
-            if constexpr (WIDTH == 160) *out = fused_launch<6, NS>(c, p, (int)grid, nterms, nsteps);
-            else if constexpr (WIDTH > 64) *out = fused_launch<8, NS>(c, p, (int)grid, nterms, nsteps);
-            else if (c.fast_state && SPLIT == 3 && NS == 4 && c.net.nl == 8) *out = fused_launch<8, NS, true>(c, p, (int)grid, nterms, nsteps);   // the collocation kernel of the 8-layer nets
-            else *out = c.net.nl == 4 ? fused_launch<4, NS>(c, p, (int)grid, nterms, nsteps) : fused_launch<8, NS>(c, p, (int)grid, nterms, nsteps);
-            ++g_path_counts[WIDTH <= 64 ? PINN_PATH_FUSED_REGISTERS : PINN_PATH_FUSED_LDS];
-            return 1;
-        } else {
-            return 0;
-        }
-    }
-
-    // the 3-D head through the fused LDS-operand kernel: 10 hidden layers of padded width 128 (BASELINE configs[4])
-    // (NS = 5: the collocation head; NS = 1, round 6: a value-only side set -- source, initial or top-surface points -- through the one-stream
-    // instantiation with the same parked one-slot layout, so that no set of a 3-D training step is left on the two-kernel path)
-    template <int NS = 5>
-    static int try_fused_3d(const Call& c, int* out) {
-        if constexpr (fused_has_3d()) {
-            if (c.net.nl != 10 || c.net.din != 4 || c.net.nout != 12) return 0;
+            DataSet sets[4];      // (NS = 1: the call's value-only sets; a single-set call is a table of one)
+            const int m = NS == 1 ? data_sets(c, sets) : 0;
+            for (int i = 0; i < m; ++i) nsteps += (sets[i].n + 16 * TILES - 1) / (16 * TILES);
+            if (NS != 1) nsteps = (c.n + 16 * TILES - 1) / (16 * TILES);
+            const long grid = fused_grid(fused_images<NS, DIN>(c.net, c.ws_bytes), nsteps);
+            if (grid == 0) return 0;
             Plan p;
-            if (((uintptr_t)c.ws & 255) != 0) return 0;
             plan_fixed<4>(c.net, c.n, p);
-            typedef Fused<Op, SPLIT, WIDTH, 10, NS, false, 4> F;
-            const size_t per_wg = (size_t)F::TILES * F::SCRATCH_BYTES;
-            if (c.ws_bytes < p.fixed_end + per_wg) return 0;
-            long grid = (long)((c.ws_bytes - p.fixed_end) / per_wg);
-            if (grid > FUSED_GRID) grid = FUSED_GRID;
-            if (g_fused_grid_cap > 0 && grid > g_fused_grid_cap) grid = g_fused_grid_cap;
-            const long nsteps = (c.n + 16 * F::TILES - 1) / (16 * F::TILES);
-            if (nsteps == 0) return 0;
-            if (grid > nsteps) grid = nsteps;
-            if (grid < FUSED_MIN_GRID && grid < nsteps) return 0;      // (see FUSED_MIN_GRID)
-            *out = fused_launch<10, NS, false, 4>(c, p, (int)grid, 12, nsteps);
-            ++g_path_counts[PINN_PATH_FUSED_LDS];
+            *out = fused_launch<decltype(k)>(c, p, (int)grid, nterms, nsteps);
+            ++g_path_counts[FUSED_PATH];
             return 1;
-        } else {
-            return 0;
-        }
+        });
     }
 
     static int wave_loss_grad(const Call& c) {
@@ -783,25 +799,17 @@ struct Host {
         bool first = true;
         for (int k = 0; k < c.nsets; ++k) {
             if (c.sets[k].n <= 0) continue;
-            Call s = c;
-            s.nsets = 0;
-            s.x = c.sets[k].x;
-            s.y = c.sets[k].y;
-            s.t = c.sets[k].t;
-            s.n = c.sets[k].n;
-            s.targets = c.sets[k].targets;
-            for (int i = 0; i < 8; ++i) s.tw[i] = c.sets[k].tw[i];
-            s.loss_out = c.sets[k].loss_out;
-            s.accumulate = c.accumulate || !first;
-            s.weights_packed = c.weights_packed || !first;
-            if ((rc = loss_grad<1, HEAD_DATA>(s, c.net.nout))) return rc;
+            if ((rc = loss_grad<1, HEAD_DATA>(set_call(c, c.sets[k], first), c.net.nout))) return rc;
             first = false;
         }
         return 0;
     }
 
+    // Forward only, one launch of the chain kernel with a head that writes per point (c.fields_out): the fields and streams (output weights
+    // zeroed) and the residual scores (with_tw: c.tw as given).  No panels, so the fixed part of the plan is all the workspace it needs; not a
+    // loss + gradient call: no path counter.
     template <int NS, int HEAD>
-    static int fields_ns(const Call& c) {
+    static int forward(const Call& c, bool with_tw) {
         Plan p;
         int rc = make_plan<NS>(c, p, false);
         if (rc) return rc;
@@ -809,51 +817,23 @@ struct Host {
         if (rc) return rc;
         ChainArgs a;
         fill_common(c, p, a);
-        for (int i = 0; i < 16; ++i) a.tw[i] = 0.0f;
+        for (int i = 0; i < 16; ++i) a.tw[i] = with_tw ? c.tw[i] : 0.0f;
         a.tile0 = 0;
         a.ntiles = p.ntiles;
         hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, nb<NS>(), NS, HEAD>), dim3(chain_blocks(p.ntiles)), dim3(256), 0, c.stream, a);
         return (int)hipGetLastError();
     }
-    static int fields(const Call& c) { return fields_ns<4, HEAD_FIELDS>(c); }
-    // pinn_wave2d_residual_score: the forward of `fields` with the score head (c.fields_out = float[n], c.tw as given); one launch, no panels,
-    // so the fixed part of the plan is all the workspace it needs; not a loss + gradient call: no path counter
-    static int wave_score(const Call& c) {
-        Plan p;
-        int rc = make_plan<4>(c, p, false);
-        if (rc) return rc;
-        rc = repack(c, p);
-        if (rc) return rc;
-        ChainArgs a;
-        fill_common(c, p, a);
-        for (int i = 0; i < 16; ++i) a.tw[i] = c.tw[i];
-        a.tile0 = 0;
-        a.ntiles = p.ntiles;
-        hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, nb<4>(), 4, HEAD_SCORE>), dim3(chain_blocks(p.ntiles)), dim3(256), 0, c.stream, a);
-        return (int)hipGetLastError();
-    }
-
-    // pinn_plate2d_residual_score / pinn_nc3d_residual_score: wave_score with five streams; split-precision variants only, like their loss calls
-    template <int HEAD>
-    static int score5(const Call& c) {
-        if constexpr (SPLIT == 3) {
-            Plan p;
-            int rc = make_plan<5>(c, p, false);
-            if (rc) return rc;
-            rc = repack(c, p);
-            if (rc) return rc;
-            ChainArgs a;
-            fill_common(c, p, a);
-            for (int i = 0; i < 16; ++i) a.tw[i] = c.tw[i];
-            a.tile0 = 0;
-            a.ntiles = p.ntiles;
-            hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, nb<5>(), 5, HEAD>), dim3(chain_blocks(p.ntiles)), dim3(256), 0, c.stream, a);
-            return (int)hipGetLastError();
-        }
+    static int fields(const Call& c) { return forward<4, HEAD_FIELDS>(c, false); }
+    static int wave_score(const Call& c) { return forward<4, HEAD_SCORE>(c, true); }      // pinn_wave2d_residual_score
+    // pinn_plate2d_residual_score (`aux` = frozen streams) / pinn_nc3d_residual_score: five streams; split-precision variants only, like their loss calls
+    static int plate_score(const Call& c) {
+        if constexpr (SPLIT == 3) return forward<5, HEAD_SCORE_PLATE>(c, true);
         return PINN_ERR_PRECISION;
     }
-    static int plate_score(const Call& c) { return score5<HEAD_SCORE_PLATE>(c); }
-    static int nc3d_score(const Call& c) { return score5<HEAD_SCORE3D>(c); }
+    static int nc3d_score(const Call& c) {
+        if constexpr (SPLIT == 3) return forward<5, HEAD_SCORE3D>(c, true);
+        return PINN_ERR_PRECISION;
+    }
 
     // 5-stream family (plate): split-precision variants only
     static int plate_loss_grad(const Call& c) {
@@ -881,48 +861,19 @@ struct Host {
         return PINN_ERR_PRECISION;
     }
     static int streams(const Call& c) {
-        if constexpr (SPLIT == 3) return fields_ns<5, HEAD_FIELDS>(c);
+        if constexpr (SPLIT == 3) return forward<5, HEAD_FIELDS>(c, false);
         return PINN_ERR_PRECISION;
     }
 
     // ---- pinn_stream_loss_grad_multi: the stream-target sets of a pre-training loss in one launch of fused_sets_kernel
-    // compiled for 4 hidden layers of padded width <= 64 in the split modes (the reference's 4 x 20 distance / particular nets, PLATE:527-559)
-    static constexpr bool sets_has() { return SPLIT == 3 && WIDTH <= 64; }
-    // scratch images a workspace holds for it (the rule of try_fused_sets AND of pinn_path_for)
-    static long sets_images(const NetDesc& net, size_t ws_bytes) {
-        if constexpr (sets_has()) {
-            typedef Fused<Op, SPLIT, WIDTH, 4, 5, false, 3, 1> F;
-            Plan p;
-            plan_fixed<4>(net, 1, p);
-            const size_t per_wg = (size_t)F::TILES * F::SCRATCH_BYTES;
-            if (ws_bytes < p.fixed_end + per_wg) return 0;
-            return (long)((ws_bytes - p.fixed_end) / per_wg);
-        } else {
-            return 0;
-        }
-    }
-    static float sets_wmax(const Call& c) {
-        float wmax = 0.0f;
-        for (int k = 0; k < c.n_ssets; ++k)
-            for (int s = 0; s < 5; ++s)
-                for (int o = 0; o < 8; ++o) { const float v = c.ssets[k].w[s][o] < 0 ? -c.ssets[k].w[s][o] : c.ssets[k].w[s][o]; if (v > wmax) wmax = v; }
-        return wmax;
-    }
-    // returns 1 if the fused launch ran (rc in *out), 0 if it does not apply (the caller then runs the sets one by one)
+    // (kind <5, 3, 1> of with_fused).  Returns 1 if the fused launch ran (rc in *out), 0 if it does not apply (the caller then runs the sets one by one)
     static int try_fused_sets(const Call& c, float wmax, int* out) {
-        if constexpr (sets_has()) {
-            typedef Fused<Op, SPLIT, WIDTH, 4, 5, false, 3, 1> F;
+        if (c.prof_ms != nullptr || ((uintptr_t)c.ws & 255) != 0) return 0;
+        return with_fused<5, 3, 1>(c.net, 0, [&](auto key) {
+            typedef typename decltype(key)::F F;
             static_assert(F::WG_ACC_BYTES <= FUSED_ACC_BYTES, "accumulator area of the plan");
             static_assert((size_t)FUSED_GRID * F::TILES * FUSED_MAX_STREAM_SETS * 8 <= (size_t)MAX_BLOCKS * 4 * LOSS_SLOTS_3D, "loss partials of the plan");
             static_assert(FUSED_MAX_STREAM_SETS == PINN_MAX_STREAM_SETS, "set table");
-            if (c.net.nl != 4 || c.prof_ms != nullptr) return 0;
-            if (((uintptr_t)c.ws & 255) != 0) return 0;
-            Plan p;
-            plan_fixed<4>(c.net, 1, p);
-            long grid = sets_images(c.net, c.ws_bytes);
-            if (grid == 0) return 0;
-            if (grid > FUSED_GRID) grid = FUSED_GRID;
-            if (g_fused_grid_cap > 0 && grid > g_fused_grid_cap) grid = g_fused_grid_cap;
             StreamSetTable T;
             LossOuts8 lo;
             long s0 = 0;
@@ -947,63 +898,34 @@ struct Host {
             T.step0[FUSED_MAX_STREAM_SETS] = s0;
             T.nsets = c.n_ssets;
             const long nsteps = s0;
-            if (nsteps == 0) return 0;
-            if (grid > nsteps) grid = nsteps;
-            if (grid < FUSED_MIN_GRID && grid < nsteps) return 0;      // (see FUSED_MIN_GRID)
+            const long grid = fused_grid(fused_images<5, 3, 1>(c.net, c.ws_bytes), nsteps);
+            if (grid == 0) return 0;
+            Plan p;
+            plan_fixed<4>(c.net, 1, p);
             int rc = repack(c, p);
             if (rc) { *out = rc; return 1; }
-            char* b = static_cast<char*>(c.ws);
+            // (the points are the table's; no XCD tail: a workgroup's steps ascend by the grid, which the per-set sums rely on)
             FusedArgs a;
-            a.net = c.net;
-            a.pw = packed(c, p);
-            a.pw.frags = reinterpret_cast<const u32x4*>(b + p.frags_fused);
-            a.frags_bytes = (unsigned)((size_t)FI::total(c.net.nl) * FUSED_PARTS * 64 * sizeof(u32x4));
-            a.x = a.y = a.t = a.z = nullptr;      // (the table's)
-            a.n = 0;
-            a.nsteps = nsteps;
-            for (int k = 0; k < 4; ++k) { a.sx[k] = c.sx[k]; a.ox[k] = c.ox[k]; }
-            a.c1 = a.c2 = a.G = a.rho = 0.0f;
-            for (int i = 0; i < 16; ++i) a.tw[i] = 0.0f;
-            a.targets = nullptr;
-            a.aux = nullptr;
-            a.nsets = 0;
-            for (int k = 0; k < 4; ++k) {
-                a.set_step0[k] = 0;
-                a.set_x[k] = a.set_y[k] = a.set_t[k] = a.set_z[k] = a.set_targets[k] = a.set_aux[k] = nullptr;
-                a.set_n[k] = 0;
-                a.set_head[k] = 0;
-                for (int i = 0; i < 16; ++i) a.set_tw[k][i] = 0.0f;
-            }
-            a.set_step0[4] = 0;
-            a.scratch = reinterpret_cast<u32x4*>(b + p.panels);
-            a.loss_part = reinterpret_cast<float*>(b + p.loss_part);
-            a.partial = reinterpret_cast<float*>(b + p.partial);
-            a.wg_acc = reinterpret_cast<u32x4*>(b + p.wg_acc);
-            a.dbg = nullptr;
-            a.block0 = 0;
-            a.grid = (int)grid;
-            a.n_plain = 0x7fffffffffffffffL;      // (no XCD tail: a workgroup's steps ascend by the grid, which the per-set sums rely on)
+            fused_args(c, p, (int)grid, nsteps, 0, 0, 0, a);
             // the weights are only ever used normalised; where the weight gradient takes fp16 adjoints (Fused::ZDB) the head scales its seeds
             // by ZDB_SEED_SCALE into the normal range and the reduction takes the factor back
             float scale = wmax;
             if constexpr (F::WG_HI) scale *= 1.0f / F::ZDB_SEED_SCALE;
             const int ring_slot = c.ring ? c.ring->begin(c.stream, 5) : -1;
-            hipLaunchKernelGGL((fused_sets_kernel<Op, SPLIT, WIDTH, 4>), dim3((int)grid), dim3(512), 0, c.stream, a, T);
+            hipLaunchKernelGGL((fused_sets_kernel<Op, SPLIT, WIDTH, decltype(key)::NL>), dim3((int)grid), dim3(512), 0, c.stream, a, T);
             if (c.ring) c.ring->end(ring_slot, c.stream);
             if ((rc = (int)hipGetLastError())) { *out = rc; return 1; }
             hipLaunchKernelGGL((reduce_grad_loss_sets_kernel<0>), dim3((c.net.nparams + 63) / 64 + c.n_ssets), dim3(256), 0, c.stream, (const float*)a.partial,
                                (int)grid, c.net.nparams, scale, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, c.net.nout, c.n_ssets,
-                               (int)FUSED_MAX_STREAM_SETS, lo, (const int*)(b + p.wflags), repack_blocks(c.net));
+                               (int)FUSED_MAX_STREAM_SETS, lo, (const int*)(static_cast<char*>(c.ws) + p.wflags), repack_blocks(c.net));
             *out = (int)hipGetLastError();
-            ++g_path_counts[PINN_PATH_FUSED_REGISTERS];
+            ++g_path_counts[FUSED_PATH];
             return 1;
-        } else {
-            return 0;
-        }
+        });
     }
     static int stream_sets_loss_grad(const Call& c) {
         if constexpr (SPLIT == 3) {
-            const float wmax = sets_wmax(c);
+            const float wmax = stream_sets_wmax(c);
             int rc = 0;
             if (c.use_fused && try_fused_sets(c, wmax, &rc)) return rc;
             // every other case: the sets one after the other on pinn_stream_loss_grad's path, under the call's one normalisation
@@ -1014,20 +936,7 @@ struct Host {
                     if ((rc = (int)hipMemsetAsync(ss.loss_out, 0, (size_t)c.net.nout * sizeof(float), c.stream))) return rc;
                     continue;
                 }
-                Call s = c;
-                s.n_ssets = 0;
-                s.x = ss.x;
-                s.y = ss.y;
-                s.t = ss.t;
-                s.n = ss.n;
-                s.aux = ss.targets;
-                for (int i = 0; i < 5; ++i)
-                    for (int o = 0; o < 8; ++o) s.w5[i][o] = ss.w[i][o];
-                s.w5_norm = wmax;
-                s.loss_out = ss.loss_out;
-                s.accumulate = c.accumulate || !first;
-                s.weights_packed = c.weights_packed || !first;
-                if ((rc = loss_grad<5, HEAD_STREAMS>(s, c.net.nout))) return rc;
+                if ((rc = loss_grad<5, HEAD_STREAMS>(set_call(c, ss, wmax, first), c.net.nout))) return rc;
                 first = false;
             }
             if (first && !c.accumulate) return (int)hipMemsetAsync(c.grad_out, 0, (size_t)c.net.nparams * sizeof(float), c.stream);
@@ -1039,7 +948,7 @@ struct Host {
     static int nc3d_loss_grad(const Call& c) {
         if constexpr (SPLIT == 3) {
             int rc = 0;
-            if (c.use_fused && try_fused_3d(c, &rc)) return rc;
+            if (c.use_fused && (try_fused<5, 4>(c, &rc, 12))) return rc;
             return loss_grad<5, HEAD_NC3D>(c, 12);
         }
         return PINN_ERR_PRECISION;
@@ -1047,20 +956,20 @@ struct Host {
     static int nc3d_data_loss_grad(const Call& c) {
         if constexpr (SPLIT == 3) {
             int rc = 0;
-            if (c.use_fused && try_fused_3d<1>(c, &rc)) return rc;
+            if (c.use_fused && (try_fused<1, 4>(c, &rc, 12))) return rc;
             return loss_grad<1, HEAD_DATA3D>(c, c.net.nout);
         }
         return PINN_ERR_PRECISION;
     }
     static int nc3d_fields(const Call& c) {
-        if constexpr (SPLIT == 3) return fields_ns<5, HEAD_FIELDS3D>(c);
+        if constexpr (SPLIT == 3) return forward<5, HEAD_FIELDS3D>(c, false);
         return PINN_ERR_PRECISION;
     }
 
     static const Impl* impl() {
         static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
                                &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
-                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score};
+                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score, &cache_policy};
         return &I;
     }
 };
