@@ -34,6 +34,9 @@ def main():
     ap.add_argument("--precision", default="f16x3")
     ap.add_argument("--refine-every", type=int, default=0, help="residual-adaptive refinement of the collocation set every N Adam steps (0 = off)")
     ap.add_argument("--refine-frac", type=float, default=0.05, help="fraction of the collocation rows offered for replacement at each refinement")
+    ap.add_argument("--refine-device", choices=["off", "top", "sample"], default="off",
+                    help="with --refine-every: draw the candidates on the device inside train(refine=...) instead of on the host -- 'top' takes the "
+                         "highest-scoring ones, 'sample' draws them with probability ~ score / mean + 1; the source disc is excluded by keys")
     a = ap.parse_args()
 
     if "RANK" in os.environ:
@@ -55,7 +58,15 @@ def main():
         model = DeepHPMConfined(c["Collo"], c["SRC"], c["IC"], c["FIXED"], None, c["uv_layers"], None, None, c["lb"], c["ub"], uvDir=a.load,
                                 precision=a.precision, verbose=rank == 0)
     t0 = time.time()
-    if a.iters and a.refine_every > 0:
+    if a.iters and a.refine_every > 0 and a.refine_device != "off":
+        # the same loop inside train(): candidates drawn on the device (stream = round * world + rank: every rank and round its own points)
+        n_rep = max(1, int(a.refine_frac * c["Collo"].shape[0]))
+        hist = model.train(iter=a.iters, learning_rate=a.lr, batch_num=a.batch_num,
+                           refine=dict(every=a.refine_every, candidates=4 * n_rep, n_replace=n_rep, seed=7919, select=a.refine_device,
+                                       exclude=[tuple(c["source"])]))
+        if rank == 0:
+            print("Adam: loss %.4e -> %.4e" % (hist[-1][0], hist[-1][-1]))
+    elif a.iters and a.refine_every > 0:
         # Adam in blocks of --refine-every steps; between blocks the lowest-scoring rows give way to higher-scoring fresh candidates
         # (Latin hypercube in the box minus the source disc, like the set itself; every rank draws its own)
         xc, yc, r = c["source"]

@@ -83,7 +83,8 @@ enum {
     PINN_ERR_LAYERS = -2,      /* unsupported layer list (see pinn_supported_width) */
     PINN_ERR_PRECISION = -3,   /* unknown precision_mode */
     PINN_ERR_WORKSPACE = -4,   /* workspace smaller than pinn_min_workspace_bytes() or misaligned */
-    PINN_ERR_SIZE = -5,        /* n < 0 (n == 0 is a valid empty batch: zero sums, zero / untouched gradient); pinn_select_k: n >= 2^31 or k outside 0 .. n */
+    PINN_ERR_SIZE = -5,        /* n < 0 (n == 0 is a valid empty batch: zero sums, zero / untouched gradient); pinn_select_k: n >= 2^31 or k outside 0 .. n;
+                                  pinn_sample_box / pinn_refine_keys: n >= 2^31, n_balls outside 0 .. PINN_MAX_BALLS, a ball's ndim outside {2, 3} */
     PINN_ERR_COLLECTIVE = -6,  /* pinn_p2p_*: not connected; a coarse-grained buffer across devices (pinn_p2p_connect); or a rank did not arrive within the
                                 * bounded wait of some call (pinn_p2p_set_timeout_ms, default 30 s) -- that call's buffer is then NaN on this rank */
     PINN_ERR_RANGE = -7,       /* pinn_wave2d_loss_grad_checked: gradient non-finite even on the two-kernel path with the reverse pass scaled by 2^-24 */
@@ -206,6 +207,55 @@ int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int 
 size_t pinn_select_workspace_bytes(int64_t n);
 int pinn_select_k(const float* score, int64_t n, int64_t k, int largest, int32_t* idx_out,
                   void* workspace, size_t ws_bytes, void* stream);
+
+/* Candidate points drawn on the device: n points uniform in the box [lo, hi] of dim = 3 (x, y, t) or 4 (x, y, z, t) columns, written to the
+ * DEVICE arrays x, y, (z), t of n floats (z is NULL iff dim == 3; lo / hi are host arrays of dim entries).  Replaces a host generator
+ * (pointsets.lhs), the float64 -> float32 conversion and the upload in front of a residual-score call.
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), counter-based: point i reads the block
+ *              counter = (lo32 idx, hi32 idx, stream_id, 0), key = (lo32 seed, hi32 seed), idx = first + i; coordinate k of the point, in the
+ *              order x, y, (z), t, is made from output word r_k
+ *   value      u = (r_k >> 8) * 2^-24;  min(fma(u, (float)(hi[k] - lo[k]), (float)lo[k]), (float)hi[k]) -- the difference in double, ONE fma
+ * Determinism: no state and no host RNG; a point is a function of (seed, stream_id, idx, lo, hi) alone, whatever the grid, so the call
+ * (first + m, n - m) gives the tail of the call (first, n), and ranks / rounds that use distinct stream ids get distinct points without
+ * coordination.  One launch, no workspace, no host synchronisation; n == 0 is a valid no-op.
+ * Errors: n < 0 or n >= 2^31: PINN_ERR_SIZE; dim outside {3, 4}: PINN_ERR_LAYERS; a NULL array: PINN_ERR_NULL. */
+int pinn_sample_box(uint64_t seed, uint32_t stream_id, uint64_t first, int64_t n, int dim,
+                    const double lo[4], const double hi[4],
+                    float* x, float* y, float* z, float* t, void* stream);
+
+/* Selection keys from scores: what stands between a residual-score call and pinn_select_k when regions are excluded or points are to be DRAWN
+ * with probability proportional to a residual measure instead of taken greedily.  Replaces host-side rejection of candidates (DelSrcPT,
+ * DelHolePT) and a host-side weighted draw.  score, x, y, z, key_out are DEVICE arrays of n floats; balls is a HOST array.
+ *   excluded        a point inside any of the n_balls balls: squared distance in fp32 over the first ndim coordinates (z may be NULL when no
+ *                   ball has ndim == 3; x, y too when n_balls == 0), against the fp32 square of the radius; d2 < r2 excludes, and d2 == r2 as
+ *                   well when keep_boundary == 0 (the two conventions of DelSrcPT)
+ *   PINN_KEYS_MASK    key = score, -inf where excluded; a NaN score stays NaN.  One launch.
+ *   PINN_KEYS_SAMPLE  a score that is not finite or is negative counts as excluded too.  q = score^power (the score itself at power == 1,
+ *                   sqrtf at 0.5, powf otherwise), m = the mean of q over the points not excluded, p = q / (float)m + (float)c (the quotient
+ *                   taken as 0 when m == 0 or no point is valid), u = ((r_0 >> 9) + 0.5) * 2^-23 from the Philox block of pinn_sample_box
+ *                   with the last counter word 1 instead of 0, and  key = logf(p) - logf(-logf(u)),  -inf where excluded or p is not
+ *                   positive.  The k largest keys (pinn_select_k with largest = 1) are then a weighted sample without replacement, P ~ p: the
+ *                   Efraimidis-Spirakis / Gumbel top-k construction.  Two launches.
+ * Determinism: m is accumulated in fp64 as per-workgroup partial sums over contiguous index ranges, which every workgroup of the second launch
+ * adds again in the same fixed order; no floating-point atomics; the noise is a function of (seed, stream_id, first + i).  The keys are a
+ * function of the arguments alone.  No host synchronisation.
+ * `workspace` is device memory of pinn_refine_keys_workspace_bytes(n) bytes (0 for an n the call rejects), 256-byte aligned, scratch of the
+ * call.  n == 0 is a valid no-op.
+ * Errors: n < 0, n >= 2^31, n_balls outside 0 .. PINN_MAX_BALLS or an ndim outside {2, 3}: PINN_ERR_SIZE; an unknown mode: PINN_ERR_PRECISION;
+ * a NULL array that is needed: PINN_ERR_NULL; short or misaligned workspace: PINN_ERR_WORKSPACE. */
+typedef struct {
+    double centre[3];
+    double radius;
+    int ndim;                  /* 2: disc in (x, y), 3: ball in (x, y, z) */
+    int keep_boundary;         /* != 0: points ON the boundary stay */
+} pinn_ball;
+#define PINN_MAX_BALLS 4
+enum { PINN_KEYS_MASK = 0, PINN_KEYS_SAMPLE = 1 };
+size_t pinn_refine_keys_workspace_bytes(int64_t n);
+int pinn_refine_keys(const float* score, int64_t n, const float* x, const float* y, const float* z,
+                     const pinn_ball* balls, int n_balls, int mode, double power, double c,
+                     uint64_t seed, uint32_t stream_id, uint64_t first,
+                     float* key_out, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- plate-with-hole family (PLATE = PlateHoleQuarter/train/train.py); precision_mode must be a split mode ---------------
  * Streams of one net at raw or normalised (x,y,t): streams_out is SoA [5][n_out][n] = Y, dY/dx, dY/dy, dY/dt, d2Y/dt2.

@@ -48,6 +48,31 @@ class StreamSet(C.Structure):
                 ("weights", (C.c_float * 8) * 5), ("loss_terms_out", C.c_void_p)]
 
 
+MAX_BALLS = 4                      # PINN_MAX_BALLS
+KEYS_MODE = {"mask": 0, "sample": 1}             # PINN_KEYS_*
+
+
+class Ball(C.Structure):
+    """pinn_ball of include/pinn_hip.h"""
+    _fields_ = [("centre", C.c_double * 3), ("radius", C.c_double), ("ndim", C.c_int), ("keep_boundary", C.c_int)]
+
+
+def ball_array(balls):
+    """(xc, yc, r) discs and (xc, yc, zc, r) balls as a pinn_ball array, the boundary excluded with the inside (keep_boundary = 0); a Ball
+    structure is taken as it is"""
+    out = (Ball * max(len(balls), 1))()
+    for k, b in enumerate(balls):
+        if isinstance(b, Ball):
+            out[k] = b
+            continue
+        v = [float(a) for a in b]
+        if len(v) not in (3, 4):
+            raise ValueError("an excluded region is (xc, yc, r) or (xc, yc, zc, r)")
+        centre = v[:-1] + [0.0] * (4 - len(v))
+        out[k] = Ball((C.c_double * 3)(*centre), v[-1], len(v) - 1, 0)
+    return out
+
+
 class AdamState(C.Structure):
     """pinn_adam_state of include/pinn_hip.h"""
     _fields_ = [("m", C.c_void_p), ("v", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
@@ -141,6 +166,13 @@ class PinnLib:
         L.pinn_select_workspace_bytes.restype = sz
         L.pinn_select_k.argtypes = [vp, i64, i64, i32, vp, vp, sz, vp]
         L.pinn_select_k.restype = i32
+        u64, u32 = C.c_uint64, C.c_uint32
+        L.pinn_sample_box.argtypes = [u64, u32, u64, i64, i32, pf64, pf64, vp, vp, vp, vp, vp]
+        L.pinn_sample_box.restype = i32
+        L.pinn_refine_keys_workspace_bytes.argtypes = [i64]
+        L.pinn_refine_keys_workspace_bytes.restype = sz
+        L.pinn_refine_keys.argtypes = [vp, i64, vp, vp, vp, C.POINTER(Ball), i32, i32, f64, f64, u64, u32, u64, vp, vp, sz, vp]
+        L.pinn_refine_keys.restype = i32
         L.pinn_plate2d_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, vp, i32, i32, vp, sz, vp]
         L.pinn_plate2d_loss_grad.restype = i32
         L.pinn_plate2d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, i32, vp, sz, vp]
@@ -415,6 +447,23 @@ class PinnLib:
     def select_k(self, score, n, k, largest, idx_out, ws, ws_bytes, stream=0):
         rc = self.lib.pinn_select_k(score, int(n), int(k), int(bool(largest)), idx_out, ws, int(ws_bytes), stream)
         self.check(rc, "pinn_select_k")
+
+    def sample_box(self, seed, stream_id, first, n, lo, hi, cols, stream=0):
+        """pinn_sample_box.  cols: the 3 (x, y, t) or 4 (x, y, z, t) device pointers; lo / hi: as many bounds."""
+        dim = len(cols)
+        x, y, z, t = (cols[0], cols[1], None, cols[2]) if dim == 3 else (tuple(cols) + (None,) * 4)[:4]
+        d4 = lambda v: (C.c_double * 4)(*([float(a) for a in v] + [0.0] * 4)[:4])
+        rc = self.lib.pinn_sample_box(int(seed), int(stream_id), int(first), int(n), dim, d4(lo), d4(hi), x, y, z, t, stream)
+        self.check(rc, "pinn_sample_box")
+
+    def refine_keys_workspace_bytes(self, n) -> int:
+        return int(self.lib.pinn_refine_keys_workspace_bytes(int(n)))
+
+    def refine_keys(self, score, n, x, y, z, balls, mode, power, c, seed, stream_id, first, key_out, ws, ws_bytes, stream=0):
+        """pinn_refine_keys.  balls: see ball_array; mode: 'mask' | 'sample'."""
+        rc = self.lib.pinn_refine_keys(score, int(n), x, y, z, ball_array(balls), len(balls), KEYS_MODE[mode], float(power), float(c), int(seed),
+                                       int(stream_id), int(first), key_out, ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_refine_keys")
 
     def net_streams(self, params, layers, x, y, t, n, lb, ub, normalize, streams_out, prec, ws, ws_bytes, stream=0):
         rc = self.lib.pinn_net_streams(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),

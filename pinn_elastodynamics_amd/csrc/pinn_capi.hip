@@ -4,6 +4,7 @@
 #include "pinn_fp32.hpp"
 #include "pinn_lbfgs.hpp"
 #include "pinn_select.hpp"
+#include "pinn_sample.hpp"
 
 #ifndef PINN_VARIANTS_DEF
 #define PINN_VARIANTS_DEF "pinn_variants.def"     // experiments (tools/exp_build.sh) build a one-variant library
@@ -623,6 +624,55 @@ int pinn_select_k(const float* score, int64_t n, int64_t k, int largest, int32_t
     if (((uintptr_t)workspace & 255) != 0 || ws_bytes < select::WS_BYTES) return PINN_ERR_WORKSPACE;
     if (k == 0) return PINN_OK;
     return select::launch(score, (uint32_t)n, (uint32_t)k, largest != 0, idx_out, workspace, static_cast<hipStream_t>(stream));
+}
+
+int pinn_sample_box(uint64_t seed, uint32_t stream_id, uint64_t first, int64_t n, int dim, const double lo[4], const double hi[4], float* x, float* y,
+                    float* z, float* t, void* stream) {
+    if (n < 0 || n >= (int64_t)1 << 31) return PINN_ERR_SIZE;
+    if (dim != 3 && dim != 4) return PINN_ERR_LAYERS;
+    if (!lo || !hi || (n > 0 && (!x || !y || !t || (dim == 4 && !z)))) return PINN_ERR_NULL;
+    if (n == 0) return PINN_OK;
+    float* const cols[4] = {x, y, dim == 4 ? z : t, dim == 4 ? t : nullptr};
+    return sample::launch_box(seed, stream_id, first, (uint32_t)n, dim, lo, hi, cols, static_cast<hipStream_t>(stream));
+}
+
+size_t pinn_refine_keys_workspace_bytes(int64_t n) { return (n < 0 || n >= (int64_t)1 << 31) ? 0 : sample::WS_BYTES; }
+
+int pinn_refine_keys(const float* score, int64_t n, const float* x, const float* y, const float* z, const pinn_ball* balls, int n_balls, int mode,
+                     double power, double c, uint64_t seed, uint32_t stream_id, uint64_t first, float* key_out, void* workspace, size_t ws_bytes,
+                     void* stream) {
+    static_assert(PINN_MAX_BALLS == sample::MAX_BALLS, "pinn_hip.h and pinn_sample.hpp disagree");
+    if (n < 0 || n >= (int64_t)1 << 31 || n_balls < 0 || n_balls > PINN_MAX_BALLS) return PINN_ERR_SIZE;
+    if (mode != PINN_KEYS_MASK && mode != PINN_KEYS_SAMPLE) return PINN_ERR_PRECISION;
+    if (!workspace || (n_balls > 0 && !balls) || (n > 0 && (!score || !key_out || (n_balls > 0 && (!x || !y))))) return PINN_ERR_NULL;
+    sample::KeyArgs a;
+    a.n_balls = n_balls;
+    for (int b = 0; b < sample::MAX_BALLS; ++b) {
+        sample::Ball& B = a.balls[b];
+        B = sample::Ball{{0.f, 0.f, 0.f}, -1.f, 2, 0};
+        if (b >= n_balls) continue;
+        if (balls[b].ndim != 2 && balls[b].ndim != 3) return PINN_ERR_SIZE;
+        if (balls[b].ndim == 3 && n > 0 && !z) return PINN_ERR_NULL;
+        for (int k = 0; k < 3; ++k) B.c[k] = (float)balls[b].centre[k];
+        B.r2 = (float)balls[b].radius * (float)balls[b].radius;
+        B.ndim = balls[b].ndim;
+        B.closed = balls[b].keep_boundary == 0;
+    }
+    if (((uintptr_t)workspace & 255) != 0 || ws_bytes < sample::WS_BYTES) return PINN_ERR_WORKSPACE;
+    if (n == 0) return PINN_OK;
+    a.score = score;
+    a.x = x;
+    a.y = y;
+    a.z = z;
+    a.n = (uint32_t)n;
+    a.pow_kind = power == 1.0 ? sample::POW_ONE : (power == 0.5 ? sample::POW_SQRT : sample::POW_GENERAL);
+    a.power = (float)power;
+    a.c = (float)c;
+    a.seed = seed;
+    a.first = first;
+    a.stream_id = stream_id;
+    a.key_out = key_out;
+    return sample::launch_keys(a, mode == PINN_KEYS_SAMPLE, workspace, static_cast<hipStream_t>(stream));
 }
 
 int pinn_net_streams(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .net_api import NetApi, read_checkpoint, truncated_normal, write_checkpoint
-from .refine import candidate_array, pair_replacements, refine_sharded_set, score_weights  # noqa: F401
+from .refine import Candidates, candidate_array, pair_replacements, refine_sharded_set, schedule, score_weights  # noqa: F401
 
 # multipliers of (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss_NB, loss_FIX) in the total loss
 LOSS_LAYOUT = {
@@ -472,7 +472,7 @@ class DeepHPM(NetApi):
         xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, t)]
         return self._score_device(xs, self._score_weights(weights)).detach().cpu().numpy().reshape(-1, 1)
 
-    def refine_collocation(self, candidates, n_replace, weights=None):
+    def refine_collocation(self, candidates, n_replace, weights=None, *, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
         """Residual-adaptive refinement that keeps the set's size: score this rank's rows of the collocation set and the ``candidates``
         [Nc,3] (x, y, t) on the device, take the K = min(n_replace, Nc, rows) highest-scoring candidates and the K lowest-scoring rows
         (engine.select_k), pair them (pair_replacements: highest candidate against lowest row) and overwrite row j with candidate j only
@@ -481,10 +481,18 @@ class DeepHPM(NetApi):
         Data parallel: no collective -- every rank refines ITS OWN rows with the candidates IT is given, so callers must pass rank-distinct
         candidates (the same candidates on every rank would be inserted once per rank).  The host copies of a rank then show its own
         replacements only, which is all that rank ever uploads.
+        ``candidates`` may be an INT: that many points are drawn on the device in ``box`` = (lo, hi), default (lb, ub), by
+        engine.sample_box(seed, stream) -- counter-based, so the points are a function of (seed, stream, index) alone; ``stream`` defaults to
+        round * world + rank, ``round`` counting this model's device-drawn refinements: ranks and rounds get distinct, reproducible candidates
+        with no coordination.  ``exclude``: discs (xc, yc, r) whose inside and boundary never enter the set (the source disc, a hole: single
+        points there reach scores 1e6 times the median).  ``select="sample"``: the K candidates are DRAWN without replacement with probability
+        ~ score^power / mean + c (engine.refine_keys: Gumbel top-k) instead of taken greedily -- the row rule stays: a candidate goes in only
+        where its score is strictly larger than the row's.  With any of these the result also holds ``candidates``: the inserted points, host
+        [replaced, 3]; ``candidate_indices`` are sample indices of the draw.  An array, select="top" and no exclude: exactly the calls above.
         Returns dict(replaced, rows, candidate_indices, score_replaced_max, score_inserted_min): how many rows changed, their row numbers in the
         whole set and the candidates that took their places (pairing order), the largest score that left and the smallest that came in (None
         when nothing was replaced).  Synchronises once (the indices come to the host)."""
-        C = candidate_array(candidates, 3, "(x, y, t)")
+        C = Candidates(self, candidates, 3, "(x, y, t)", select, power, c, seed, stream, box, exclude)
         return refine_sharded_set(self, C, n_replace, self._score_weights(weights), ("x_c", "y_c", "t_c"))
 
     def callback(self, loss):                        # INF:278-280, SEMI:285-288
@@ -625,14 +633,17 @@ class DeepHPM(NetApi):
     # ------------------------------------------------------------------------------------------
     # training drivers
     # ------------------------------------------------------------------------------------------
-    def train(self, iter, learning_rate, batch_num, record="pre"):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None):
         """Adam loop of INF:282-319: contiguous collocation blocks, ``iter`` steps per block, all
         side sets fed whole to every block.  Returns the per-step lists
         (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss).  ``record="pre"`` (default): each recorded value is the loss
         the step's gradient was taken at -- free.  ``record="post"``: the reference's own bookkeeping, every term re-evaluated
-        AFTER the update (its four to six extra sess.run calls per step, INF:308-317) -- one more loss+gradient evaluation per step."""
+        AFTER the update (its four to six extra sess.run calls per step, INF:308-317) -- one more loss+gradient evaluation per step.
+        ``refine``: None, or dict(every, candidates, n_replace, ...) -- refine_collocation with that many device-drawn candidates behind every
+        ``every``-th step of this call (refine.RefineSchedule; the further entries are refine_collocation's keywords)."""
         if record not in ("pre", "post"):
             raise ValueError("record must be 'pre' or 'post'")
+        sched, step = schedule(self, refine), 0
         loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss = [], [], [], [], []
         P = self.n_params
         col_num = self._n_collo
@@ -662,6 +673,9 @@ class DeepHPM(NetApi):
                 if self.verbose and it % 10 == 0 and self.rank == 0:
                     tm = self._terms_from_sums(rec[it].detach().cpu().numpy().reshape(len(_SLOTS), 8), idx_end - idx_start)
                     print('It: %d, Loss: %.3e' % (it, tm["loss"]))
+                if sched is not None:
+                    step += 1
+                    sched.after_step(step)
             sums = rec.detach().cpu().numpy().reshape(iter, len(_SLOTS), 8)
             self._check_collective()                 # (behind the block's one host synchronisation)
             if iter > 0 and not bool(torch.isfinite(self.theta).all()):
@@ -772,9 +786,9 @@ class DeepHPMConfined(DeepHPM):
             if layers is not None:
                 self._aux_nets[name] = self.load_NN(path, layers) if path else xavier_init(layers, np.random.default_rng(seed + off))
 
-    def train(self, iter, learning_rate, batch_num, record="pre"):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None):
         """CONF:373-408 returns three lists: (loss_f_uv, loss_f_s, loss)."""
-        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record)
+        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record, refine)
         return loss_f_uv, loss_f_s, loss
 
     def save_NN(self, fileDir, TYPE=''):

@@ -320,6 +320,35 @@ class HipEngine(LbfgsMixin):
         self.lib.select_k(score.data_ptr(), n, k, largest, out.data_ptr(), self._select_ws_ptr, self._select_ws_bytes, self._stream())
         return out
 
+    def sample_box(self, n: int, lo, hi, seed: int, stream: int = 0, first: int = 0):
+        """n points uniform in the box [lo, hi] (3 bounds: columns x, y, t; 4: x, y, z, t) as a tuple of device columns (pinn_sample_box):
+        Philox4x32-10 keyed by ``seed``, point i a function of (seed, stream, first + i) alone.  No synchronisation."""
+        dim = len(lo)
+        cols = tuple(torch.empty(int(n), dtype=torch.float32, device=self.device) for _ in range(dim))
+        self.lib.sample_box(seed, stream, first, n, lo, hi, [c.data_ptr() for c in cols], self._stream())
+        return cols
+
+    def refine_keys(self, score, cols, balls=(), mode: str = "mask", power: float = 1.0, c: float = 1.0, seed: int = 0, stream: int = 0, first: int = 0):
+        """Selection keys of the device scores ``score`` at the device columns ``cols`` (x, y, t) or (x, y, z, t) (pinn_refine_keys): -inf
+        inside the ``balls`` -- (xc, yc, r) discs, (xc, yc, zc, r) balls --; otherwise the score (mode 'mask') or log p + Gumbel noise with
+        p = score^power / mean + c (mode 'sample'), so that select_k(keys, k) draws k points without replacement, P ~ p.  No synchronisation."""
+        self._chk(score)
+        n = score.numel()
+        for v in cols:
+            self._chk(v, n)
+        ws = self.__dict__.get("_keys_ws")
+        if ws is None:                      # (the size does not depend on n: one buffer per engine)
+            nbytes = self.lib.refine_keys_workspace_bytes(0)
+            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            self._keys_ws = ws
+            self._keys_ws_ptr, self._keys_ws_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        x, y = (cols[0].data_ptr(), cols[1].data_ptr()) if len(cols) >= 2 else (None, None)      # (no columns: fine without balls)
+        z = cols[2].data_ptr() if len(cols) == 4 else None
+        self.lib.refine_keys(score.data_ptr(), n, x, y, z, list(balls), mode, power, c, seed, stream, first,
+                             out.data_ptr(), self._keys_ws_ptr, self._keys_ws_bytes, self._stream())
+        return out
+
     # ---- plate family (5 streams: value, d/dx, d/dy, d/dt, d2/dt2) --------------------------------------------------
     def net_streams(self, params, x, y, t, lb, ub, normalize):
         """Returns [5, n_out, n]: the net's outputs, their first derivatives and the second time derivative."""

@@ -19,7 +19,7 @@ import torch
 
 from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, unpack_params, xavier_init  # noqa: F401
 from .net_api import NetApi, read_checkpoint, write_checkpoint
-from .refine import candidate_array, refine_sharded_set, score_weights
+from .refine import Candidates, refine_sharded_set, schedule, score_weights
 
 OUT = ("u", "v", "w", "ut", "vt", "wt", "s11", "s22", "s33", "s12", "s13", "s23")
 _SLOTS = ("collo", "IC", "SRC", "NB")          # 16 floats each in the loss-sum buffer
@@ -206,13 +206,21 @@ class NavierCauchy3D(NetApi):
         xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, z, t)]
         return self._score_device(xs, self._score_weights(weights)).detach().cpu().numpy().reshape(-1, 1)
 
-    def refine_collocation(self, candidates, n_replace, weights=None):
+    def refine_collocation(self, candidates, n_replace, weights=None, *, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
         """Residual-adaptive refinement that keeps the set's size, exactly as elastic_wave.DeepHPM.refine_collocation with four columns:
         ``candidates`` [Nc,4] (x, y, z, t); the K = min(n_replace, Nc, rows) lowest-scoring rows of this rank give way to the K highest-scoring
         candidates where those score strictly higher.  N, the 1/N weights, the block boundaries of train(batch_num), the workspace and the
         shards stay; the host copies (x_c, y_c, z_c, t_c) follow on copies.  Data parallel: no collective, pass rank-distinct candidates.
+        ``candidates`` may be an INT: that many points are drawn on the device in ``box`` = (lo, hi), default (lb, ub), by
+        engine.sample_box(seed, stream) -- counter-based, so the points are a function of (seed, stream, index) alone; ``stream`` defaults to
+        round * world + rank, ``round`` counting this model's device-drawn refinements: ranks and rounds get distinct, reproducible candidates
+        with no coordination.  ``exclude``: discs (xc, yc, r) -- cylinders along z -- or balls (xc, yc, zc, r) whose inside and boundary never enter the set (the source disc, a hole: single
+        points there reach scores 1e6 times the median).  ``select="sample"``: the K candidates are DRAWN without replacement with probability
+        ~ score^power / mean + c (engine.refine_keys: Gumbel top-k) instead of taken greedily -- the row rule stays: a candidate goes in only
+        where its score is strictly larger than the row's.  With any of these the result also holds ``candidates``: the inserted points, host
+        [replaced, 4]; ``candidate_indices`` are sample indices of the draw.  An array, select="top" and no exclude: exactly the calls above.
         Returns dict(replaced, rows, candidate_indices, score_replaced_max, score_inserted_min).  Synchronises once."""
-        C = candidate_array(candidates, 4, "(x, y, z, t)")
+        C = Candidates(self, candidates, 4, "(x, y, z, t)", select, power, c, seed, stream, box, exclude)
         return refine_sharded_set(self, C, n_replace, self._score_weights(weights), ("x_c", "y_c", "z_c", "t_c"))
 
     def callback(self, loss):
@@ -289,10 +297,12 @@ class NavierCauchy3D(NetApi):
         return out
 
     # ---- training drivers ---------------------------------------------------------------------------------------------
-    def train(self, iter, learning_rate, batch_num):
+    def train(self, iter, learning_rate, batch_num, refine=None):
         """Adam loop with the reference's block-sequential batching (SEMI:290-328): returns the per-step lists
-        (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss) -- the loss each step's gradient was taken at."""
+        (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss) -- the loss each step's gradient was taken at.  ``refine``: None, or
+        dict(every, candidates, n_replace, ...): refine_collocation with device-drawn candidates behind every ``every``-th step of this call."""
         P, L = self.n_params, len(_SLOTS)
+        sched, step = schedule(self, refine), 0
         hist = ([], [], [], [], [])
         for i in range(batch_num):
             lo, hi = int(i * self._n_collo / batch_num), int((i + 1) * self._n_collo / batch_num)
@@ -310,6 +320,9 @@ class NavierCauchy3D(NetApi):
                 rec[it].copy_(self._buf[P:])
                 self.adam_t += 1
                 self.engine.adam_step(self.theta, self.adam_m, self.adam_v, self._buf[:P], learning_rate, self.adam_t)
+                if sched is not None:
+                    step += 1
+                    sched.after_step(step)
             if iter > 0 and not bool(torch.isfinite(self.theta).all()):
                 raise FloatingPointError("parameters became non-finite during train(): lower the learning rate or raise engine.adjoint_shift")
             sums = rec.detach().cpu().numpy().reshape(iter, L, 16)

@@ -18,7 +18,7 @@ import torch
 
 from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, relax_adjoint_shift, unpack_params, xavier_init  # noqa: F401
 from .net_api import NetApi, read_checkpoint, write_checkpoint
-from .refine import candidate_array, device_columns, empty_result, score_weights, select_pairs, update_host_columns
+from .refine import Candidates, empty_result, schedule, score_weights, select_pairs, update_host_columns
 
 _EPS = float(np.finfo(float).eps)
 BFGS_OPTIONS = {   # PLATE:220-247
@@ -268,7 +268,7 @@ class PINN(NetApi):
             return np.zeros((0, 1), dtype=np.float32)
         return self._score_device(xs, self._frozen_at(xs), w).detach().cpu().numpy().reshape(-1, 1)
 
-    def refine_collocation(self, candidates, n_replace, weights=None):
+    def refine_collocation(self, candidates, n_replace, weights=None, *, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
         """Residual-adaptive refinement that keeps the set's size (the rule of elastic_wave.DeepHPM.refine_collocation): score this rank's rows
         with the frozen streams it holds and the ``candidates`` [Nc,3] (x, y, t) with frozen streams computed once for them; the
         K = min(n_replace, Nc, rows) lowest-scoring rows give way to the K highest-scoring candidates where those score strictly higher.
@@ -277,20 +277,26 @@ class PINN(NetApi):
         point do not depend on its place in the batch (a point is one row of a tile), so refresh_frozen() afterwards gives the same bits
         (tests/test_gpu_refine_families.py holds that).  n_collo, the 1/N weights, the workspace and the shards stay; x_c, y_c, t_c follow on
         copies.  Data parallel: no collective, every rank refines its own rows: pass rank-distinct candidates.
+        ``candidates`` may be an INT (that many points drawn on the device in ``box``, default (lb, ub); stream = round * world + rank unless
+        given), ``exclude`` a list of discs (xc, yc, r) -- the hole --, ``select="sample"`` draws the K candidates with probability
+        ~ score^power / mean + c: all as in DeepHPM.refine_collocation.  The frozen streams of device-drawn candidates come from _frozen_at
+        as for host candidates and follow the row.  The result then also holds ``candidates``, the inserted points [replaced, 3].
         Returns dict(replaced, rows, candidate_indices, score_replaced_max, score_inserted_min) like DeepHPM's; ``rows`` are row numbers of
         the whole set.  Synchronises once."""
-        C = candidate_array(candidates, 3, "(x, y, t)")
+        C = Candidates(self, candidates, 3, "(x, y, t)", select, power, c, seed, stream, box, exclude)
         w = self._score_weights(weights)
         s0, e0 = self._shard(0, self.n_collo)
-        K = min(int(n_replace), C.shape[0], e0 - s0)
+        K = min(int(n_replace), C.n, e0 - s0)
         out = empty_result()
+        if not C.plain:
+            out["candidates"] = np.zeros((0, 3))
         if K <= 0:
             return out
-        cand = device_columns(C, self.device)
+        cand = C.columns(self.eng["uv"], self.device)
         frozen_cand = self._frozen_at(cand)
         s_rows = self._score_device(self._collo, self._frozen_collo, w)
         s_cand = self._score_device(cand, frozen_cand, w, packed=True)
-        ri, ci, rs, cs = select_pairs(self.eng["uv"], s_rows, s_cand, K)
+        ri, ci, rs, cs = select_pairs(self.eng["uv"], s_rows, s_cand, K, C.keys(self.eng["uv"], s_cand, cand))
         m = int(ri.numel())
         if m == 0:
             return out
@@ -298,8 +304,11 @@ class PINN(NetApi):
             self._collo[k][ri] = cand[k][ci]
         self._frozen_collo[..., ri] = frozen_cand[..., ci]
         r_host, c_host = ri.cpu().numpy() + s0, ci.cpu().numpy()
-        update_host_columns(self, ("x_c", "y_c", "t_c"), r_host, c_host, C)
+        pts = C.inserted(cand, ci, c_host)
+        update_host_columns(self, ("x_c", "y_c", "t_c"), r_host, np.arange(m), pts)
         out.update(replaced=m, rows=r_host, candidate_indices=c_host, score_replaced_max=float(rs.max()), score_inserted_min=float(cs.min()))
+        if not C.plain:
+            out["candidates"] = pts
         return out
 
     def callback(self, loss):
@@ -351,10 +360,12 @@ class PINN(NetApi):
         out["loss"] = 10.0 * (out["loss_f_uv"] + out["loss_f_s"] + out["loss_HOLE"])
         return out
 
-    def train(self, iter, learning_rate):
+    def train(self, iter, learning_rate, refine=None):
         """Adam loop of PLATE:475-506 (whole collocation set every step).  Returns (loss_f_uv, loss_f_s, loss_HOLE, loss) lists;
-        as in elastic_wave.DeepHPM.train the recorded values are those the step's gradient was taken at."""
+        as in elastic_wave.DeepHPM.train the recorded values are those the step's gradient was taken at.  ``refine``: None, or
+        dict(every, candidates, n_replace, ...): refine_collocation with device-drawn candidates behind every ``every``-th step of this call."""
         P = self.theta["uv"].numel()
+        sched = schedule(self, refine)
         rec = torch.empty((iter, 16), dtype=torch.float32, device=self.device)
 
         def probe():
@@ -373,6 +384,8 @@ class PINN(NetApi):
                 self.eng["uv"].adam_step(self.theta["uv"], self.adam_m, self.adam_v, self._buf[:P], learning_rate, self.adam_t)
             if self.verbose and it % 10 == 0 and self.rank == 0:
                 print('It: %d, Loss: %.6e' % (it, self._terms(rec[it].detach().cpu().numpy())["loss"]))
+            if sched is not None:
+                sched.after_step(it + 1)
         sums = rec.detach().cpu().numpy()
         self._check_collective()                     # (behind the loop's one host synchronisation)
         tms = [self._terms(s) for s in sums]

@@ -3,6 +3,10 @@ plate_hole.PINN).  The rule: score this rank's rows and the candidates on the de
 highest-scoring candidates and the K lowest-scoring rows (engine.select_k), pair them -- highest candidate against lowest row -- and overwrite
 a row ONLY where its candidate scores strictly higher.  The set keeps its size, so the 1/N weights, the block boundaries of train(batch_num),
 the workspace and the data-parallel shards stay what they were.  No collective: every rank refines its own rows with the candidates it is given.
+Candidates may also be DRAWN ON THE DEVICE (an int instead of an array: engine.sample_box, stream = round * world + rank, so ranks and rounds get
+distinct, reproducible points), regions may be excluded, and the K candidates may be drawn with probability ~ score^power / mean + c instead of
+taken greedily (engine.refine_keys turns the scores into keys, select_k then runs on the keys).  The rule for the rows stays: a candidate goes in
+only where its SCORE is strictly larger than the row's, and an excluded candidate (key -inf) never does.
 """
 from __future__ import annotations
 
@@ -48,11 +52,102 @@ def empty_result():
             "score_replaced_max": None, "score_inserted_min": None}
 
 
-def select_pairs(engine, s_rows, s_cand, K):
-    """the two selections and the pairing on the device: (rows, candidates, row scores, candidate scores) of the pairs to replace"""
-    ci = engine.select_k(s_cand, K, largest=True).long()
+def pair_by_key(cand_idx, cand_key, cand_score, row_idx, row_score):
+    """pair_replacements where the candidates were selected by a KEY (engine.refine_keys) that is not their score: candidates by key descending,
+    rows by score ascending, pair j kept only where the candidate's SCORE is strictly larger than the row's and its key is not -inf (an excluded
+    candidate, selected because fewer than K were valid, is never inserted)."""
+    oc = torch.sort(cand_key, descending=True, stable=True).indices
+    orr = torch.sort(row_score, descending=False, stable=True).indices
+    ci, ck, cs, ri, rs = cand_idx[oc], cand_key[oc], cand_score[oc], row_idx[orr], row_score[orr]
+    keep = (cs > rs) & (ck > float("-inf"))
+    return ri[keep], ci[keep], rs[keep], cs[keep]
+
+
+def select_pairs(engine, s_rows, s_cand, K, keys=None):
+    """the two selections and the pairing on the device: (rows, candidates, row scores, candidate scores) of the pairs to replace; with
+    ``keys`` the candidates are selected and ordered by them (pair_by_key)"""
+    ci = engine.select_k(s_cand if keys is None else keys, K, largest=True).long()
     ri = engine.select_k(s_rows, K, largest=False).long()
-    return pair_replacements(ci, s_cand[ci], ri, s_rows[ri])
+    if keys is None:
+        return pair_replacements(ci, s_cand[ci], ri, s_rows[ri])
+    return pair_by_key(ci, keys[ci], s_cand[ci], ri, s_rows[ri])
+
+
+class Candidates:
+    """The candidates of one refine_collocation call.  ``candidates``: a float64 [Nc, ncols] array (converted and uploaded by ``columns``) or an
+    int: that many points drawn on the device in ``box`` = (lo, hi) -- default the model's (lb, ub) -- by engine.sample_box(seed, stream), the
+    stream by default  round * world + rank  with ``round`` the model's count of device-drawn refinements so far.  ``plain``: an array, greedy
+    selection, nothing excluded -- the path that existed before keys did, which makes the engine calls it always made."""
+
+    def __init__(self, model, candidates, ncols, names, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
+        if select not in ("top", "sample"):
+            raise ValueError("select must be 'top' or 'sample'")
+        self.select, self.power, self.c = select, float(power), float(c)
+        self.exclude = [tuple(float(v) for v in b) for b in exclude]
+        for b in self.exclude:
+            if len(b) != 3 and not (len(b) == 4 and ncols == 4):
+                raise ValueError("exclude: (xc, yc, r)" + (" or (xc, yc, zc, r)" if ncols == 4 else ""))
+        self.seed = 0 if seed is None else int(seed)
+        self.drawn = isinstance(candidates, (int, np.integer)) and not isinstance(candidates, bool)
+        self.stream = 0 if stream is None else int(stream)
+        if self.drawn:
+            self.C, self.n = None, int(candidates)
+            if self.n < 0:
+                raise ValueError("candidates: a number of points to draw must not be negative")
+            rnd = getattr(model, "_refine_round", 0)
+            model._refine_round = rnd + 1
+            if stream is None:
+                self.stream = rnd * model.world + model.rank
+            lo, hi = (model.lb, model.ub) if box is None else box
+            self.lo, self.hi = ([float(v) for v in np.asarray(b, dtype=np.float64).reshape(-1)] for b in (lo, hi))
+            if len(self.lo) != ncols or len(self.hi) != ncols:
+                raise ValueError(f"box: (lo, hi) with {ncols} bounds each = {names}")
+        else:
+            self.C = candidate_array(candidates, ncols, names)
+            self.n = self.C.shape[0]
+        self.plain = not self.drawn and select == "top" and not self.exclude
+
+    def columns(self, engine, device):
+        """the candidates as device columns"""
+        if self.drawn:
+            return engine.sample_box(self.n, self.lo, self.hi, self.seed, self.stream)
+        return device_columns(self.C, device)
+
+    def keys(self, engine, s_cand, cols):
+        """what select_k runs on: None on the plain path (the scores themselves), else engine.refine_keys of the scores"""
+        if self.plain:
+            return None
+        return engine.refine_keys(s_cand, cols, self.exclude, "sample" if self.select == "sample" else "mask", self.power, self.c, self.seed, self.stream)
+
+    def inserted(self, cols, ci, c_host):
+        """the inserted points as a host [m, ncols] float64 array (pairing order)"""
+        if self.C is not None:
+            return self.C[c_host]
+        return torch.stack([a[ci] for a in cols], dim=1).cpu().numpy().astype(np.float64)
+
+
+class RefineSchedule:
+    """train(..., refine=dict(every=E, candidates=Nc, n_replace=K, **keywords of refine_collocation)): refine_collocation behind every E-th
+    step of the call.  ``after_step(j)`` with j = 1, 2, ... counted over the whole train call."""
+
+    def __init__(self, model, refine):
+        kw = dict(refine)
+        try:
+            self.every, cand, n_replace = int(kw.pop("every")), kw.pop("candidates"), int(kw.pop("n_replace"))
+        except KeyError as e:
+            raise ValueError(f"refine: missing {e.args[0]!r} (need every, candidates, n_replace)") from None
+        if self.every < 1 or not isinstance(cand, (int, np.integer)) or isinstance(cand, bool):
+            raise ValueError("refine: every >= 1 and candidates an int (points drawn on the device each time)")
+        self.model, self.args, self.kw, self.results = model, (int(cand), n_replace), kw, []
+
+    def after_step(self, step):
+        if step % self.every == 0:
+            self.results.append(self.model.refine_collocation(*self.args, **self.kw))
+
+
+def schedule(model, refine):
+    """the RefineSchedule of train(refine=...), or None for refine=None"""
+    return None if refine is None else RefineSchedule(model, refine)
 
 
 def update_host_columns(model, names, r_host, c_host, C):
@@ -67,17 +162,22 @@ def update_host_columns(model, names, r_host, c_host, C):
 
 def refine_sharded_set(model, C, n_replace, w, names):
     """refine_collocation of the classes that keep the set as host columns plus device shards (_collo_host / _collo_full / _collo_cache, _rows,
-    _shard, _n_collo) and score through ``model._score_device(columns, weights, packed=...)``.  ``C``: candidates [Nc, len(names)] float64."""
+    _shard, _n_collo) and score through ``model._score_device(columns, weights, packed=...)``.  ``C``: a Candidates, or candidates
+    [Nc, len(names)] float64."""
+    if not isinstance(C, Candidates):
+        C = Candidates(model, C, len(names), names)
     s0, e0 = model._shard(0, model._n_collo)
-    K = min(int(n_replace), C.shape[0], e0 - s0)
+    K = min(int(n_replace), C.n, e0 - s0)
     out = empty_result()
+    if not C.plain:
+        out["candidates"] = np.zeros((0, len(names)))
     if K <= 0:
         return out
     rows = model._rows(0, model._n_collo)
-    cand = device_columns(C, model.device)
+    cand = C.columns(model.engine, model.device)
     s_rows = model._score_device(rows, w)
     s_cand = model._score_device(cand, w, packed=True)
-    ri, ci, rs, cs = select_pairs(model.engine, s_rows, s_cand, K)
+    ri, ci, rs, cs = select_pairs(model.engine, s_rows, s_cand, K, C.keys(model.engine, s_cand, cand))
     m = int(ri.numel())
     model._collo_cache = {}
     if m == 0:
@@ -86,8 +186,11 @@ def refine_sharded_set(model, C, n_replace, w, names):
         for k in range(len(names)):
             model._collo_full[k][s0 + ri] = cand[k][ci]
     r_host, c_host = ri.cpu().numpy() + s0, ci.cpu().numpy()
-    update_host_columns(model, names, r_host, c_host, C)
+    pts = C.inserted(cand, ci, c_host)
+    update_host_columns(model, names, r_host, np.arange(m), pts)
     for k in range(len(names)):
-        model._collo_host[k][r_host] = C[c_host, k].astype(np.float32)
+        model._collo_host[k][r_host] = pts[:, k].astype(np.float32)
     out.update(replaced=m, rows=r_host, candidate_indices=c_host, score_replaced_max=float(rs.max()), score_inserted_min=float(cs.min()))
+    if not C.plain:
+        out["candidates"] = pts
     return out

@@ -254,6 +254,8 @@ inline float __builtin_amdgcn_exp2f(float x) { return exp2f(x); }
 inline float __builtin_amdgcn_rcpf(float x) { return 1.0f / x; }
 inline float __builtin_amdgcn_sqrtf(float x) { return sqrtf(x); }
 inline float __builtin_amdgcn_rsqf(float x) { return 1.0f / sqrtf(x); }
+inline float __fmaf_rn(float a, float b, float c) { return fmaf(a, b, c); }           // one rounding, as v_fma_f32
+inline unsigned __umulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
 inline void __builtin_amdgcn_s_setprio(int) {}
 inline void __builtin_amdgcn_sched_barrier(int) {}
 inline void __builtin_amdgcn_s_sleep(int) { emu::spin_yield(); }
