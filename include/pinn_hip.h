@@ -197,6 +197,37 @@ int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int 
                                const float term_weights[7], float* score_out,
                                int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
+/* The predict head of the wave family -- what predict evaluates (INF:337-347: net_uv INF:201-211 and net_e INF:213-219 on a point set) in one
+ * launch that carries the STRAIN streams only: value, d/dx, d/dy.  The time tangent, which no predict output reads, is not computed.
+ *   out is a DEVICE array, SoA [8][n], rows in the order  u, v, s11, s22, s12, e11, e22, e12
+ *   u, v, s11, s22, s12 = outputs 0, 1, 4, 5, 6;  e11 = du/dx, e22 = dv/dy, e12 = du/dy + dv/dx  (the velocities ut, vt are not part of predict)
+ * The forward is the one of pinn_wave2d_fields in the same mode for the streams carried (the same per-stream kernel code; the carried streams
+ * agree with the fields call bit for bit), the head adds one rounding in e12.  Every compiled family (all widths and operand modes, any depth)
+ * and PINN_PREC_FP32; one launch behind the repack, so pinn_min_workspace_bytes() is enough for any n (PINN_PREC_FP32 walks the points in
+ * passes); honours PINN_FLAG_WEIGHTS_PACKED; n == 0 is a valid no-op.  Not a loss + gradient call: pinn_debug_path_counts does not count it.
+ * layers must end in 7 outputs.  Timing: profiles/predict_head_calls.txt. */
+int pinn_wave2d_predict(const float* params_flat, const int* layers, int n_layers,
+                        const float* x, const float* y, const float* t, int64_t n,
+                        const double lb[3], const double ub[3], int normalize,
+                        float* out, int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* Per-field error sums of a predict output against reference data on the device: what the relative L2 comparison with FEM frames needs
+ * (sqrt(sums[0][j] / sums[1][j]) per field), without downloading the fields.
+ *   pred      DEVICE array [pred_rows][n], e.g. the output of a predict call
+ *   rows      HOST array of n_rows entries: row rows[j] of pred is compared with row j of ref (FEM frames carry u, v, s11, s22, s12, no strains)
+ *   ref       DEVICE array [n_rows][n]
+ *   sums_out  DEVICE array of 2 * n_rows doubles, [2][n_rows]:  sum_i (pred[rows[j]][i] - ref[j][i])^2,  then  sum_i ref[j][i]^2
+ * Differences and squares are formed in fp64.  Determinism: per-workgroup partial sums over contiguous index ranges, added by one final pass
+ * in a fixed order (the scheme of pinn_refine_keys' mean); no floating-point atomics; the sums are a function of the arguments alone.  Rows of
+ * pred that are not selected are never read.  No host synchronisation; n == 0 writes zeros.
+ * `workspace` is device memory of pinn_field_error_workspace_bytes(n, n_rows) bytes (0 for arguments the call rejects), 256-byte aligned.
+ * Errors: n < 0, n >= 2^31, n_rows outside 1 .. 16, pred_rows < 1 or a rows[j] outside 0 .. pred_rows - 1: PINN_ERR_SIZE; a NULL array that is
+ * needed: PINN_ERR_NULL; short or misaligned workspace: PINN_ERR_WORKSPACE. */
+size_t pinn_field_error_workspace_bytes(int64_t n, int n_rows);
+int pinn_field_error_sums(const float* pred, int64_t pred_rows, const int* rows, int n_rows,
+                          const float* ref, int64_t n, double* sums_out,
+                          void* workspace, size_t ws_bytes, void* stream);
+
 /* Deterministic top-k / bottom-k selection on the device: which k of the n floats in `score` are the largest (largest != 0) or the smallest.
  *   order   each float maps to a uint32 key that is monotone in the float order (sign-flip map: -0 < +0, a positive NaN above +inf, a negative
  *           NaN below -inf); elements are ordered by key (descending if `largest`, else ascending), then by index ascending
@@ -301,6 +332,23 @@ int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int
                                 const float* frozen_streams, double E, double mu, double rho,
                                 const float term_weights[5], float* score_out,
                                 int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* The predict head of the plate family -- what predict evaluates (PLATE:561-570: the composite fields and strains of PLATE:358-388 on a point
+ * set) in one launch of the uv net that carries the strain streams only: value, d/dx, d/dy (no time tangent, no second time derivative).
+ *   frozen_streams  the [2][5][5][n] array of pinn_plate2d_loss_grad at the same points.  ONLY stream rows 0, 1, 2 (value, x, y) of D and of P
+ *                   are read; rows 3 and 4 may hold anything
+ *   composite       F0 = P0 + D0 N0,  Fk = Pk + Dk N0 + D0 Nk  (k = 1, 2), as pinn_plate2d_residual_score forms it
+ *   out is a DEVICE array, SoA [8][n], rows in the order  u, v, s11, s22, s12, e11, e22, e12
+ *                   = F0[u], F0[v], F0[s11], F0[s22], F0[s12], F1[u], F2[v], F2[u] + F1[v]
+ * The forward is the one of pinn_net_streams in the same mode for the streams carried (the same per-stream kernel code), the head adds at
+ * most six roundings (e12).  Split modes of every compiled width and PINN_PREC_FP32 (the other 16-bit modes: PINN_ERR_PRECISION, as the loss
+ * call); any depth; one launch behind the repack, so pinn_min_workspace_bytes() is enough for any n; honours PINN_FLAG_WEIGHTS_PACKED; n == 0
+ * is a valid no-op; no path counter moves.  layers must end in 5 outputs.  Timing: profiles/predict_head_calls.txt. */
+int pinn_plate2d_predict(const float* params_flat, const int* layers, int n_layers,
+                         const float* x, const float* y, const float* t, int64_t n,
+                         const double lb[3], const double ub[3], int normalize,
+                         const float* frozen_streams, float* out,
+                         int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
 /* Replaces net_t + loss_HOLE (PLATE:452-461,192-193) and its gradient w.r.t. the uv net.
  *   frozen_and_normals: SoA [12][n] = D values (5 fields), P values (5 fields), nx, ny at the hole points

@@ -162,6 +162,14 @@ class PinnLib:
         L.pinn_net_streams.restype = i32
         L.pinn_wave2d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, i32, pf32, vp, i32, vp, sz, vp]
         L.pinn_wave2d_residual_score.restype = i32
+        L.pinn_wave2d_predict.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, i32, vp, sz, vp]
+        L.pinn_wave2d_predict.restype = i32
+        L.pinn_plate2d_predict.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, vp, i32, vp, sz, vp]
+        L.pinn_plate2d_predict.restype = i32
+        L.pinn_field_error_workspace_bytes.argtypes = [i64, i32]
+        L.pinn_field_error_workspace_bytes.restype = sz
+        L.pinn_field_error_sums.argtypes = [vp, i64, pi32, i32, vp, i64, vp, vp, sz, vp]
+        L.pinn_field_error_sums.restype = i32
         L.pinn_select_workspace_bytes.argtypes = [i64]
         L.pinn_select_workspace_bytes.restype = sz
         L.pinn_select_k.argtypes = [vp, i64, i64, i32, vp, vp, sz, vp]
@@ -440,6 +448,28 @@ class PinnLib:
                                                  int(bool(normalize)), float(E), float(mu), float(rho), int(bool(plane_strain)),
                                                  self._floats(term_weights, 7), score_out, mode_bits(prec), ws, int(ws_bytes), stream)
         self.check(rc, "pinn_wave2d_residual_score")
+
+    def wave2d_predict(self, params, layers, x, y, t, n, lb, ub, normalize, out, prec, ws, ws_bytes, stream=0):
+        """pinn_wave2d_predict: out [8][n] = u, v, s11, s22, s12, e11, e22, e12"""
+        rc = self.lib.pinn_wave2d_predict(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
+                                          int(bool(normalize)), out, mode_bits(prec), ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_wave2d_predict")
+
+    def plate2d_predict(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, out, prec, ws, ws_bytes, stream=0):
+        """pinn_plate2d_predict: frozen [2][5][5][n] (stream rows 0..2 read), out [8][n] in the order of wave2d_predict"""
+        rc = self.lib.pinn_plate2d_predict(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
+                                           int(bool(normalize)), frozen, out, mode_bits(prec), ws, int(ws_bytes), stream)
+        self.check(rc, "pinn_plate2d_predict")
+
+    def field_error_workspace_bytes(self, n, n_rows) -> int:
+        return int(self.lib.pinn_field_error_workspace_bytes(int(n), int(n_rows)))
+
+    def field_error_sums(self, pred, pred_rows, rows, ref, n, sums_out, ws, ws_bytes, stream=0):
+        """pinn_field_error_sums: sums_out (device, 2 * len(rows) doubles) = sum (pred[rows[j]] - ref[j])^2, then sum ref[j]^2"""
+        rows = [int(r) for r in rows]
+        rc = self.lib.pinn_field_error_sums(pred, int(pred_rows), (C.c_int * max(1, len(rows)))(*rows), len(rows), ref, int(n), sums_out, ws,
+                                            int(ws_bytes), stream)
+        self.check(rc, "pinn_field_error_sums")
 
     def select_workspace_bytes(self, n) -> int:
         return int(self.lib.pinn_select_workspace_bytes(int(n)))

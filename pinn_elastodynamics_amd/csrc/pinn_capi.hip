@@ -5,6 +5,7 @@
 #include "pinn_lbfgs.hpp"
 #include "pinn_select.hpp"
 #include "pinn_sample.hpp"
+#include "pinn_validate.hpp"
 
 #ifndef PINN_VARIANTS_DEF
 #define PINN_VARIANTS_DEF "pinn_variants.def"     // experiments (tools/exp_build.sh) build a one-variant library
@@ -346,7 +347,7 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
     a.head = head;
     a.din = din;
     a.second = (din == 3 && ns == 5) ? 1 : 0;
-    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head);
+    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head) || head_is_predict(head);
     int pass = 0;
     for (long p0 = 0; p0 < c.n; p0 += mmax, ++pass) {
         a.p0 = p0;
@@ -434,11 +435,11 @@ static int run_loss_grad(Call& c, const Impl* impl, float* loss_out, float* grad
     if (!impl) return fp32_call(c, head, nterms, ns, din);
     return (impl->*call)(c);
 }
-// (forward only: fields, streams and the residual scores -- the scores are no loss + gradient calls and not counted as a path)
+// (forward only: fields, streams, the residual scores and the predict heads -- the last two are not counted as a path)
 static int run_forward(Call& c, const Impl* impl, float* out, int (*Impl::*call)(const Call&), int head, int ns, int din = 3) {
     c.fields_out = out;
     if (c.n == 0) return PINN_OK;
-    if (!impl) return fp32_call(c, head, 0, ns, din, !head_is_score(head));
+    if (!impl) return fp32_call(c, head, 0, ns, din, !head_is_score(head) && !head_is_predict(head));
     return (impl->*call)(c);
 }
 
@@ -616,6 +617,43 @@ int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int 
     return run_forward(c, impl, score_out, &Impl::wave_score, HEAD_SCORE, 4);
 }
 
+int pinn_wave2d_predict(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
+                        const double lb[3], const double ub[3], int normalize, float* out, int precision_mode, void* workspace, size_t ws_bytes,
+                        void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (n > 0 && !out) return PINN_ERR_NULL;
+    if (c.net.nout != 7) return PINN_ERR_LAYERS;
+    return run_forward(c, impl, out, &Impl::wave_predict, HEAD_PREDICT, 3);
+}
+
+size_t pinn_field_error_workspace_bytes(int64_t n, int n_rows) {
+    return (n < 0 || n >= (int64_t)1 << 31 || n_rows < 1 || n_rows > validate::MAX_ROWS) ? 0 : validate::ws_bytes(n_rows);
+}
+
+int pinn_field_error_sums(const float* pred, int64_t pred_rows, const int* rows, int n_rows, const float* ref, int64_t n, double* sums_out,
+                          void* workspace, size_t ws_bytes, void* stream) {
+    if (n < 0 || n >= (int64_t)1 << 31 || n_rows < 1 || n_rows > validate::MAX_ROWS || pred_rows < 1) return PINN_ERR_SIZE;
+    if (!rows || !sums_out || !workspace || (n > 0 && (!pred || !ref))) return PINN_ERR_NULL;
+    validate::ErrArgs a;
+    for (int j = 0; j < validate::MAX_ROWS; ++j) a.rows[j] = 0;
+    for (int j = 0; j < n_rows; ++j) {
+        if (rows[j] < 0 || rows[j] >= pred_rows) return PINN_ERR_SIZE;
+        a.rows[j] = rows[j];
+    }
+    if (((uintptr_t)workspace & 255) != 0 || ws_bytes < validate::ws_bytes(n_rows)) return PINN_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) return (int)hipMemsetAsync(sums_out, 0, (size_t)2 * n_rows * sizeof(double), st);
+    a.pred = pred;
+    a.ref = ref;
+    a.n = (uint32_t)n;
+    a.n_rows = n_rows;
+    a.sums_out = sums_out;
+    return validate::launch(a, workspace, st);
+}
+
 size_t pinn_select_workspace_bytes(int64_t n) { return (n < 0 || n >= (int64_t)1 << 31) ? 0 : select::WS_BYTES; }
 
 int pinn_select_k(const float* score, int64_t n, int64_t k, int largest, int32_t* idx_out, void* workspace, size_t ws_bytes, void* stream) {
@@ -716,6 +754,19 @@ int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int
     for (int i = 0; i < 5; ++i) c.tw[i] = term_weights[i];
     c.aux = frozen_streams;
     return run_forward(c, impl, score_out, &Impl::plate_score, HEAD_SCORE_PLATE, 5);
+}
+
+int pinn_plate2d_predict(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
+                         const double lb[3], const double ub[3], int normalize, const float* frozen_streams, float* out, int precision_mode,
+                         void* workspace, size_t ws_bytes, void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (n > 0 && (!frozen_streams || !out)) return PINN_ERR_NULL;
+    if (c.net.nout != 5) return PINN_ERR_LAYERS;
+    c.aux = frozen_streams;
+    return run_forward(c, impl, out, &Impl::plate_predict, HEAD_PREDICT_PLATE, 3);
 }
 
 int pinn_plate2d_traction_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y,

@@ -243,12 +243,20 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 //               (pinn_plate2d_residual_score)
 // HEAD_SCORE3D: forward only, 5 first-order streams, 4 inputs, 12 outputs: the same for the twelve residuals of HEAD_NC3D
 //               (pinn_nc3d_residual_score)
+// HEAD_PREDICT: forward only, the STRAIN streams only -- 3 streams (value, x, y), no time tangent: what predict evaluates (INF:337-347), written
+//               through `fields_out` as [8][n] = u, v, s11, s22, s12, e11, e22, e12 (pinn_wave2d_predict)
+// HEAD_PREDICT_PLATE: forward only, 3 streams (value, x, y): the composite P + D*N of the plate from stream rows 0..2 of the frozen blocks in
+//               `aux` (rows 3, 4 are never read), [8][n] in the same order (PLATE:561-570; pinn_plate2d_predict)
+//               (The 4-input family has no such head: value + x, y, z are four streams, and the four-stream instantiations of padded width 128
+//               -- HEAD_SCORE's too -- spill registers where the five-stream ones fit, so at the 10 x 128 net it measured slower than
+//               HEAD_FIELDS3D: 4.83 against 4.64 ms per 1 M points.)
 enum { HEAD_WAVE = 0, HEAD_DATA = 1, HEAD_FIELDS = 2, HEAD_PLATE = 3, HEAD_TRACTION = 4, HEAD_STREAMS = 5, HEAD_NC3D = 6, HEAD_DATA3D = 7,
-       HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11 };
+       HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11, HEAD_PREDICT = 12, HEAD_PREDICT_PLATE = 13 };
 __host__ __device__ constexpr bool head_is_3d(int head) {
     return head == HEAD_NC3D || head == HEAD_DATA3D || head == HEAD_FIELDS3D || head == HEAD_SCORE3D;
 }
 __host__ __device__ constexpr bool head_is_score(int head) { return head == HEAD_SCORE || head == HEAD_SCORE_PLATE || head == HEAD_SCORE3D; }
+__host__ __device__ constexpr bool head_is_predict(int head) { return head == HEAD_PREDICT || head == HEAD_PREDICT_PLATE; }
 constexpr int LOSS_SLOTS_3D = 16;     // per-wave loss partials: 8 slots for the reference's heads, 16 for the 3-D ones
 
 struct ChainArgs {
@@ -270,8 +278,8 @@ struct ChainArgs {
     long S_tile_stride;        // in 16-bit elements
     long Z_tile_stride;
     float* loss_part;          // [total waves][8 or LOSS_SLOTS_3D] per-wave partial sums of squares
-    float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  score heads: [n]
-    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
+    float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  score heads: [n];  predict heads: [8][n]
+    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_PREDICT_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
     float w5[5][8];            // HEAD_STREAMS: per (stream, output) weights, max-normalised
 };
 
@@ -454,7 +462,10 @@ struct Chain {
     static constexpr int NPS = SPLIT == 3 ? 2 : 1;     // stored weight-fragment parts (see repack_kernel)
     static constexpr int DIN = head_is_3d(HEAD) ? 4 : 3;                       // inputs (x, y, t) or (x, y, z, t)
     static constexpr bool SECOND = NS == 5 && DIN == 3;                         // stream 4 = second time derivative (plate, PLATE:427-433)
-    static constexpr int NT = NS >= 4 ? (SECOND ? 3 : NS - 1) : 0;              // first-order tangent streams 1..NT (one per input)
+    // first-order tangent streams 1..NT (stream s differentiates by input s - 1); the predict heads carry the spatial ones only: NS = 3 of
+    // (x, y, t) -- the time tangent is the last input's and is simply not there
+    static constexpr int NT = head_is_predict(HEAD) ? NS - 1 : (NS >= 4 ? (SECOND ? 3 : NS - 1) : 0);
+    static_assert(!head_is_predict(HEAD) || NS == DIN, "predict heads: value + one tangent per space coordinate");
     static constexpr int NOG = DIN == 4 ? 16 : 8;                               // outputs every lane gathers for the head
     static constexpr int LT = DIN == 4 ? LOSS_SLOTS_3D : 8;                     // loss partial slots per wave
     static constexpr float INV_LS = 1.0f / Op::LO_SCALE;
@@ -706,7 +717,7 @@ struct Chain {
         const int wpb = blockDim.x >> 6;
         const long gwave = (long)blockIdx.x * wpb + (threadIdx.x >> 6), nwaves = (long)gridDim.x * wpb;
         const int nl = a.net.nl;
-        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD);
+        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD) || head_is_predict(HEAD);
         constexpr bool SPILL = !FWD_ONLY;
         __shared__ __attribute__((aligned(16))) char spill_lds[4 * 1024];      // one 1 KB transpose record per wave (256-thread blocks)
         char* rec = spill_lds + (threadIdx.x >> 6) * 1024;
@@ -1090,6 +1101,49 @@ struct Chain {
 #pragma unroll
                     for (int i = 0; i < 12; ++i) sc += a.tw[i] * (f[i] * f[i]);
                     if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
+                } else if constexpr (HEAD == HEAD_PREDICT) {
+                    // predict (INF:337-347): net_uv's u, v and stresses, net_e's strains (INF:216-218); streams (value, d/dx, d/dy)
+                    if (q == 0 && valid[nb]) {
+                        const float(&V)[8] = Y[0][nb];
+                        const float(&X)[8] = Y[1][nb];
+                        const float(&Yy)[8] = Y[2][nb];
+                        float* o = a.fields_out + pidx[nb];
+                        o[0 * a.n] = V[0];
+                        o[1 * a.n] = V[1];
+                        o[2 * a.n] = V[4];
+                        o[3 * a.n] = V[5];
+                        o[4 * a.n] = V[6];
+                        o[5 * a.n] = X[0];
+                        o[6 * a.n] = Yy[1];
+                        o[7 * a.n] = Yy[0] + X[1];
+                    }
+                } else if constexpr (HEAD == HEAD_PREDICT_PLATE) {
+                    // the plate's predict (PLATE:561-570): composite F = P + D*N as HEAD_SCORE_PLATE forms it, for the value stream and the
+                    // two space derivatives of u, v only; outputs (u,v,s11,s22,s12); aux = [D|P][stream][field][n], stream rows 0..2 read
+                    if (q == 0 && valid[nb]) {
+                        float* o = a.fields_out + pidx[nb];
+#pragma unroll
+                        for (int f = 0; f < 5; ++f) {
+                            const float d0 = a.aux[((long)(0 * 5 + 0) * 5 + f) * a.n + pidx[nb]];
+                            float F0 = a.aux[((long)(1 * 5 + 0) * 5 + f) * a.n + pidx[nb]];      // start from P
+                            F0 += d0 * Y[0][nb][f];
+                            o[(long)f * a.n] = F0;
+                        }
+                        float Fk[2][2];      // [stream k - 1 = x, y][field u, v]
+#pragma unroll
+                        for (int k = 1; k <= 2; ++k)
+#pragma unroll
+                            for (int f = 0; f < 2; ++f) {
+                                const float d0 = a.aux[((long)(0 * 5 + 0) * 5 + f) * a.n + pidx[nb]];
+                                const float dk = a.aux[((long)(0 * 5 + k) * 5 + f) * a.n + pidx[nb]];
+                                float F = a.aux[((long)(1 * 5 + k) * 5 + f) * a.n + pidx[nb]];
+                                F += dk * Y[0][nb][f] + d0 * Y[k][nb][f];
+                                Fk[k - 1][f] = F;
+                            }
+                        o[5 * a.n] = Fk[0][0];
+                        o[6 * a.n] = Fk[1][1];
+                        o[7 * a.n] = Fk[1][0] + Fk[0][1];
+                    }
                 } else {
                     // predict (INF:337-347): write Y and its tangent streams, [NS*nout][n]
                     if (q == 0 && valid[nb]) {

@@ -40,7 +40,7 @@ struct Fp32Args {
     float* Z;                  // [nl+1][ns][hr][m]: Z_l = adjoint of the pre-activations of weight layer l (Z_nl: nout rows)
     float* fsq;                // [FP32_TERMS][m]: squared residuals of the pass
     float* fields_out;         // fields heads: [ns][nout][n];  score heads: [n]
-    int ns;                    // streams: 1, 4 (value, x, y, t) or 5 (+ tt for din = 3; value, x, y, z, t for din = 4)
+    int ns;                    // streams: 1, 4 (value, x, y, t) or 5 (+ tt for din = 3; value, x, y, z, t for din = 4); predict heads: din (no time tangent)
     int hr;                    // row stride of S / Z: max(h, 16)
     int head;                  // HEAD_*
     int din;                   // 3 or 4
@@ -105,6 +105,40 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
         if (a.head == HEAD_FIELDS || a.head == HEAD_FIELDS3D) {
             for (int s = 0; s < ns; ++s)
                 for (int o = 0; o < NO; ++o) a.fields_out[((long)s * NO + o) * a.n + gp] = Y[s][o];
+            continue;
+        }
+        if (a.head == HEAD_PREDICT) {
+            // pinn_wave2d_predict (ns = 3: value, x, y): [8][n] = u, v, s11, s22, s12, e11, e22, e12
+            float* o = a.fields_out + gp;
+            o[0 * a.n] = Y[0][0];
+            o[1 * a.n] = Y[0][1];
+            o[2 * a.n] = Y[0][4];
+            o[3 * a.n] = Y[0][5];
+            o[4 * a.n] = Y[0][6];
+            o[5 * a.n] = Y[1][0];
+            o[6 * a.n] = Y[2][1];
+            o[7 * a.n] = Y[2][0] + Y[1][1];
+            continue;
+        }
+        if (a.head == HEAD_PREDICT_PLATE) {
+            // pinn_plate2d_predict (ns = 3): the composite of HEAD_PLATE below from stream rows 0..2 of the frozen blocks only
+            float* o = a.fields_out + gp;
+            for (int f = 0; f < 5; ++f) {
+                float F0 = a.aux[((long)(1 * 5 + 0) * 5 + f) * a.n + gp];
+                F0 += a.aux[((long)(0 * 5 + 0) * 5 + f) * a.n + gp] * Y[0][f];
+                o[(long)f * a.n] = F0;
+            }
+            float Fk[2][2];      // [stream k - 1 = x, y][field u, v]
+            for (int k = 1; k <= 2; ++k)
+                for (int f = 0; f < 2; ++f) {
+                    const float d0 = a.aux[((long)(0 * 5 + 0) * 5 + f) * a.n + gp], dk = a.aux[((long)(0 * 5 + k) * 5 + f) * a.n + gp];
+                    float F = a.aux[((long)(1 * 5 + k) * 5 + f) * a.n + gp];
+                    F += dk * Y[0][f] + d0 * Y[k][f];
+                    Fk[k - 1][f] = F;
+                }
+            o[5 * a.n] = Fk[0][0];
+            o[6 * a.n] = Fk[1][1];
+            o[7 * a.n] = Fk[1][0] + Fk[0][1];
             continue;
         }
         if (a.head == HEAD_SCORE) {

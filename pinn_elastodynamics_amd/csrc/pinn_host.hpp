@@ -127,6 +127,9 @@ struct Impl {
     // the same for the plate family (HEAD_SCORE_PLATE, `aux` = frozen streams) and the 4-input family (HEAD_SCORE3D); split modes only
     int (*plate_score)(const Call&);
     int (*nc3d_score)(const Call&);
+    // predict heads (forward only, value + space tangents): HEAD_PREDICT every compiled line; HEAD_PREDICT_PLATE split modes only
+    int (*wave_predict)(const Call&);
+    int (*plate_predict)(const Call&);
     // pinn_debug_cache_policy: the collocation kernel compiled for this net and head (asked of the F16 split-3 line of the net's width)
     int (*cache_policy)(const NetDesc&, int head, size_t* images_bytes, size_t* sums_bytes);
 };
@@ -192,6 +195,10 @@ struct Host {
     // points per wave tile = 16*NB: two blocks for narrow nets, one when the register budget is tight (wide nets, 5 streams)
     template <int NS>
     static constexpr int nb() { return (WIDTH <= 64 && NS != 5) ? 2 : 1; }
+    // The predict heads (3 streams, forward only) run ONE block per wave at every width.  Measured at padded width 64, f16x3, 1 M points
+    // (profiles/predict_head_calls.txt): two blocks need 230 + 256 registers and leave one wave per SIMD -- wave 8 x 64 0.92 ms, plate 0.94 ms --,
+    // one block 0.82 / 0.80 ms; the wider nets have one block in every head.
+    static constexpr int NB_PREDICT = 1;
     static constexpr int NP = SPLIT == 3 ? 2 : 1;
     static constexpr int NPS = SPLIT == 3 ? 2 : 1;    // stored weight-fragment parts
     static constexpr int FUSED_PARTS = SPLIT == 3 ? 3 : 1;   // ... of the fused kernel's format (repack_kernel)
@@ -808,21 +815,29 @@ struct Host {
     // Forward only, one launch of the chain kernel with a head that writes per point (c.fields_out): the fields and streams (output weights
     // zeroed) and the residual scores (with_tw: c.tw as given).  No panels, so the fixed part of the plan is all the workspace it needs; not a
     // loss + gradient call: no path counter.
-    template <int NS, int HEAD>
+    template <int NS, int HEAD, int NB = nb<NS>()>
     static int forward(const Call& c, bool with_tw) {
         Plan p;
-        int rc = make_plan<NS>(c, p, false);
+        int rc = make_plan<NS>(c, p, false);      // (no panels: only the fixed part of this plan is used -- its offsets and fixed_end do not depend on NS)
         if (rc) return rc;
+        const long ntiles = (((c.n + 16 * NB - 1) / (16 * NB)) + 1) & ~1L;      // tiles of THIS launch's block count (the plan's belong to nb<NS>())
         rc = repack(c, p);
         if (rc) return rc;
         ChainArgs a;
         fill_common(c, p, a);
         for (int i = 0; i < 16; ++i) a.tw[i] = with_tw ? c.tw[i] : 0.0f;
         a.tile0 = 0;
-        a.ntiles = p.ntiles;
-        hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, nb<NS>(), NS, HEAD>), dim3(chain_blocks(p.ntiles)), dim3(256), 0, c.stream, a);
+        a.ntiles = ntiles;
+        hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, NB, NS, HEAD>), dim3(chain_blocks(ntiles)), dim3(256), 0, c.stream, a);
         return (int)hipGetLastError();
     }
+    // pinn_wave2d_predict / pinn_plate2d_predict: the strain streams only (value, d/dx, d/dy)
+    static int wave_predict(const Call& c) { return forward<3, HEAD_PREDICT, NB_PREDICT>(c, false); }
+    static int plate_predict(const Call& c) {
+        if constexpr (SPLIT == 3) return forward<3, HEAD_PREDICT_PLATE, NB_PREDICT>(c, false);
+        return PINN_ERR_PRECISION;
+    }
+
     static int fields(const Call& c) { return forward<4, HEAD_FIELDS>(c, false); }
     static int wave_score(const Call& c) { return forward<4, HEAD_SCORE>(c, true); }      // pinn_wave2d_residual_score
     // pinn_plate2d_residual_score (`aux` = frozen streams) / pinn_nc3d_residual_score: five streams; split-precision variants only, like their loss calls
@@ -969,7 +984,8 @@ struct Host {
     static const Impl* impl() {
         static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
                                &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
-                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score, &cache_policy};
+                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score,
+                               &wave_predict, &plate_predict, &cache_policy};
         return &I;
     }
 };

@@ -22,6 +22,7 @@ import torch
 
 from .net_api import NetApi, read_checkpoint, truncated_normal, write_checkpoint
 from .refine import Candidates, candidate_array, pair_replacements, refine_sharded_set, schedule, score_weights  # noqa: F401
+from .validate import PredictMixin, schedule as validate_schedule
 
 # multipliers of (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss_NB, loss_FIX) in the total loss
 LOSS_LAYOUT = {
@@ -256,7 +257,7 @@ def lbfgs_hip(engine, theta, evaluate, n_params, loss_coeffs, options, callback=
                        success=rec["status"] in (1, 2), max_abs_grad=rec["max_abs_grad"], pairs=rec["pairs"], skipped=rec["skipped"])
 
 
-class DeepHPM(NetApi):
+class DeepHPM(NetApi, PredictMixin):
     """Drop-in for the reference's model class on the wave cases (INF:21-376)."""
 
     def __init__(self, Collo, SRC, IC, UP, uv_layers, lb, ub, ExistModel=0, modelDir='', *, case="infinite",
@@ -633,17 +634,20 @@ class DeepHPM(NetApi):
     # ------------------------------------------------------------------------------------------
     # training drivers
     # ------------------------------------------------------------------------------------------
-    def train(self, iter, learning_rate, batch_num, record="pre", refine=None):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None):
         """Adam loop of INF:282-319: contiguous collocation blocks, ``iter`` steps per block, all
         side sets fed whole to every block.  Returns the per-step lists
         (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss).  ``record="pre"`` (default): each recorded value is the loss
         the step's gradient was taken at -- free.  ``record="post"``: the reference's own bookkeeping, every term re-evaluated
         AFTER the update (its four to six extra sess.run calls per step, INF:308-317) -- one more loss+gradient evaluation per step.
         ``refine``: None, or dict(every, candidates, n_replace, ...) -- refine_collocation with that many device-drawn candidates behind every
-        ``every``-th step of this call (refine.RefineSchedule; the further entries are refine_collocation's keywords)."""
+        ``every``-th step of this call (refine.RefineSchedule; the further entries are refine_collocation's keywords).
+        ``validate``: None, or dict(every, points=(x, y, t), ref={name: column}, fields=(...)) -- the relative L2 of predict's fields against
+        ``ref`` behind every ``every``-th step (validate.ValidateSchedule): the sums stay on the device until the block's host synchronisation,
+        the results are appended to ``self.val_rec`` as (step, dict)."""
         if record not in ("pre", "post"):
             raise ValueError("record must be 'pre' or 'post'")
-        sched, step = schedule(self, refine), 0
+        sched, vsched, step = schedule(self, refine), validate_schedule(self, validate), 0
         loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss = [], [], [], [], []
         P = self.n_params
         col_num = self._n_collo
@@ -673,10 +677,15 @@ class DeepHPM(NetApi):
                 if self.verbose and it % 10 == 0 and self.rank == 0:
                     tm = self._terms_from_sums(rec[it].detach().cpu().numpy().reshape(len(_SLOTS), 8), idx_end - idx_start)
                     print('It: %d, Loss: %.3e' % (it, tm["loss"]))
-                if sched is not None:
+                if sched is not None or vsched is not None:
                     step += 1
-                    sched.after_step(step)
+                    if sched is not None:
+                        sched.after_step(step)
+                    if vsched is not None:
+                        vsched.after_step(step)
             sums = rec.detach().cpu().numpy().reshape(iter, len(_SLOTS), 8)
+            if vsched is not None:
+                vsched.flush()
             self._check_collective()                 # (behind the block's one host synchronisation)
             if iter > 0 and not bool(torch.isfinite(self.theta).all()):
                 raise FloatingPointError("parameters became non-finite during train(): residuals outgrew the 16-bit reverse pass; "
@@ -748,6 +757,17 @@ class DeepHPM(NetApi):
 
     probe = predict                                  # INF:349-359 is a verbatim copy of predict
 
+    # predict on the device (validate.PredictMixin: predict_device, predict_frames, validate): the predict head carries value, d/dx, d/dy only
+    PREDICT_FIELDS = ("u", "v", "s11", "s22", "s12", "e11", "e22", "e12")
+    PREDICT_INPUTS = ("x", "y", "t")
+    VALIDATE_FIELDS = ("u", "v", "s11", "s22", "s12")             # what FEM frames carry (pointsets.preprocess)
+
+    def _predict_engine(self):
+        return self.engine
+
+    def _predict_cols(self, xs):
+        return self.engine.wave_predict(self.theta, xs[0], xs[1], xs[2], self.lb, self.ub, self.normalize)
+
     def getloss(self):
         """INF:361-376: (loss, loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss_NB) on the full sets."""
         n = self._n_collo
@@ -786,9 +806,9 @@ class DeepHPMConfined(DeepHPM):
             if layers is not None:
                 self._aux_nets[name] = self.load_NN(path, layers) if path else xavier_init(layers, np.random.default_rng(seed + off))
 
-    def train(self, iter, learning_rate, batch_num, record="pre", refine=None):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None):
         """CONF:373-408 returns three lists: (loss_f_uv, loss_f_s, loss)."""
-        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record, refine)
+        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record, refine, validate)
         return loss_f_uv, loss_f_s, loss
 
     def save_NN(self, fileDir, TYPE=''):

@@ -94,6 +94,7 @@ class HipEngine(LbfgsMixin):
         self._ws_ptr = (self.ws.data_ptr() + 255) // 256 * 256
 
         self._lib_path = lib_path
+        self._err_ws = None                   # workspace of field_error_sums, allocated at its first call
 
     def for_layers(self, layers: Sequence[int]) -> "HipEngine":
         """A sibling engine for a net of other layer sizes (same precision mode, device and library): neural_net(X, weights, biases) of
@@ -303,6 +304,57 @@ class HipEngine(LbfgsMixin):
         self.lib.nc3d_residual_score(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), z.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
                                      E, mu, rho, term_weights, out.data_ptr(), PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr,
                                      self.ws_bytes, self._stream())
+        return out
+
+    # ---- predict heads: value + space tangents only, and the per-field error sums behind them ------------------------
+    def _predict_out(self, rows, n, out):
+        if out is None:
+            out = torch.empty((rows, n), dtype=torch.float32, device=self.device)
+        self._chk(out, rows * n)
+        return out
+
+    def wave_predict(self, params, x, y, t, lb, ub, normalize, out: Optional[torch.Tensor] = None, packed: bool = False):
+        """Returns the device tensor [8, n] = u, v, s11, s22, s12, e11, e22, e12 (pinn_wave2d_predict): the forward of ``fields`` with the
+        streams value, d/dx, d/dy only -- no time tangent."""
+        n = x.numel()
+        for v in (x, y, t):
+            self._chk(v, n)
+        self._chk(params, self.n_params)
+        out = self._predict_out(8, n, out)
+        self.lib.wave2d_predict(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, out.data_ptr(),
+                                PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr, self.ws_bytes, self._stream())
+        return out
+
+    def plate_predict(self, params, x, y, t, lb, ub, normalize, frozen, out: Optional[torch.Tensor] = None, packed: bool = False):
+        """The same for the plate family (pinn_plate2d_predict): ``frozen`` is the [2, 5, 5, n] tensor of plate_loss_grad at these points (its
+        stream rows 0..2 are read), the eight rows are those of the composite P + D*N."""
+        n = x.numel()
+        for v in (x, y, t):
+            self._chk(v, n)
+        self._chk(params, self.n_params)
+        self._chk(frozen, 50 * n)
+        out = self._predict_out(8, n, out)
+        self.lib.plate2d_predict(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, frozen.data_ptr(),
+                                 out.data_ptr(), PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr, self.ws_bytes,
+                                 self._stream())
+        return out
+
+    def field_error_sums(self, pred, rows, ref, out: Optional[torch.Tensor] = None):
+        """Per-field error sums of the device tensor ``pred`` [pred_rows, n] against ``ref`` [len(rows), n] (pinn_field_error_sums): the device
+        float64 tensor [2, len(rows)] = sum (pred[rows[j]] - ref[j])^2, then sum ref[j]^2, formed in fp64 in a fixed order.  No synchronisation."""
+        self._chk(pred)
+        rows = [int(r) for r in rows]
+        n = pred.shape[-1]
+        self._chk(ref, len(rows) * n)
+        if self._err_ws is None:            # (the size depends on the row count only: one buffer per engine, for the 16 rows a call may have)
+            nbytes = self.lib.field_error_workspace_bytes(0, 16)
+            self._err_ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            self._err_ws_ptr, self._err_ws_bytes = (self._err_ws.data_ptr() + 255) // 256 * 256, nbytes
+        if out is None:
+            out = torch.empty((2, len(rows)), dtype=torch.float64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 2 * len(rows)
+        self.lib.field_error_sums(pred.data_ptr(), pred.numel() // n if n else max(rows) + 1, rows, ref.data_ptr(), n, out.data_ptr(),
+                                  self._err_ws_ptr, self._err_ws_bytes, self._stream())
         return out
 
     def select_k(self, score, k: int, largest: bool = True):

@@ -19,6 +19,7 @@ import torch
 from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, relax_adjoint_shift, unpack_params, xavier_init  # noqa: F401
 from .net_api import NetApi, read_checkpoint, write_checkpoint
 from .refine import Candidates, empty_result, schedule, score_weights, select_pairs, update_host_columns
+from .validate import PredictMixin, schedule as validate_schedule
 
 _EPS = float(np.finfo(float).eps)
 BFGS_OPTIONS = {   # PLATE:220-247
@@ -28,7 +29,7 @@ BFGS_OPTIONS = {   # PLATE:220-247
 }
 
 
-class PINN(NetApi):
+class PINN(NetApi, PredictMixin):
     def __init__(self, Collo, HOLE, IC, LF, RT, UP, LW, DIST, uv_layers, dist_layers, part_layers, lb, ub,
                  partDir='', distDir='', uvDir='', *, precision="f16x3", engines=None, seed=1111, process_group=None, verbose=True,
                  always_reduce=False, collective="rccl", p2p_timeout_s=None):
@@ -360,12 +361,14 @@ class PINN(NetApi):
         out["loss"] = 10.0 * (out["loss_f_uv"] + out["loss_f_s"] + out["loss_HOLE"])
         return out
 
-    def train(self, iter, learning_rate, refine=None):
+    def train(self, iter, learning_rate, refine=None, validate=None):
         """Adam loop of PLATE:475-506 (whole collocation set every step).  Returns (loss_f_uv, loss_f_s, loss_HOLE, loss) lists;
         as in elastic_wave.DeepHPM.train the recorded values are those the step's gradient was taken at.  ``refine``: None, or
-        dict(every, candidates, n_replace, ...): refine_collocation with device-drawn candidates behind every ``every``-th step of this call."""
+        dict(every, candidates, n_replace, ...): refine_collocation with device-drawn candidates behind every ``every``-th step of this call.
+        ``validate``: None, or dict(every, points=(x, y, t), ref={name: column}, fields=(...)): the relative L2 of predict's fields against ``ref``
+        behind every ``every``-th step, downloaded at the loop's host synchronisation into ``self.val_rec`` as (step, dict)."""
         P = self.theta["uv"].numel()
-        sched = schedule(self, refine)
+        sched, vsched = schedule(self, refine), validate_schedule(self, validate)
         rec = torch.empty((iter, 16), dtype=torch.float32, device=self.device)
 
         def probe():
@@ -386,7 +389,11 @@ class PINN(NetApi):
                 print('It: %d, Loss: %.6e' % (it, self._terms(rec[it].detach().cpu().numpy())["loss"]))
             if sched is not None:
                 sched.after_step(it + 1)
+            if vsched is not None:
+                vsched.after_step(it + 1)
         sums = rec.detach().cpu().numpy()
+        if vsched is not None:
+            vsched.flush()
         self._check_collective()                     # (behind the loop's one host synchronisation)
         tms = [self._terms(s) for s in sums]
         return ([t["loss_f_uv"] for t in tms], [t["loss_f_s"] for t in tms], [t["loss_HOLE"] for t in tms], [t["loss"] for t in tms])
@@ -537,6 +544,24 @@ class PINN(NetApi):
     def predict(self, x_star, y_star, t_star):       # PLATE:561-570
         F = self._composite(x_star, y_star, t_star)
         return self._cols(torch.stack([F[0, 0], F[0, 1], F[0, 2], F[0, 3], F[0, 4], F[1, 0], F[2, 1], F[2, 0] + F[1, 1]]))
+
+    # predict on the device (validate.PredictMixin): D and P from net_streams as _frozen_at does, the uv net through the predict head
+    PREDICT_FIELDS = ("u", "v", "s11", "s22", "s12", "e11", "e22", "e12")
+    PREDICT_INPUTS = ("x", "y", "t")
+    VALIDATE_FIELDS = ("u", "v", "s11", "s22", "s12")
+
+    def _predict_engine(self):
+        return self.eng["uv"]
+
+    def _predict_aux(self, xs):
+        """the frozen D / P streams at the points: they do not change while the uv net trains, so train(validate=...) evaluates them once"""
+        return self._frozen_at(xs) if xs[0].numel() else None
+
+    def _predict_cols(self, xs, frozen=None):
+        if xs[0].numel() == 0:
+            return torch.empty((8, 0), dtype=torch.float32, device=self.device)
+        return self.eng["uv"].plate_predict(self.theta["uv"], xs[0], xs[1], xs[2], self.lb, self.ub, False,
+                                            self._frozen_at(xs) if frozen is None else frozen)
 
     def predict_D(self, x_star, y_star, t_star):     # PLATE:572-578
         return self.net_dist(x_star, y_star, t_star)
