@@ -15,12 +15,16 @@ follows, and the identical fused Adam step runs on every rank, so the weights st
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import Optional
 
 import numpy as np
 import torch
 
-from .net_api import NetApi, read_checkpoint, truncated_normal, write_checkpoint
+from .model_base import ShardedSetsModel
+from .net_api import write_checkpoint
+# (the optimizer and parameter helpers lived in this module before optim.py: tools and tests import them from here)
+from .optim import (BFGS_BACKENDS, LbfgsResult, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device,  # noqa: F401
+                    pack_params, relax_adjoint_shift, unpack_params, xavier_init)
 from .refine import Candidates, candidate_array, pair_replacements, refine_sharded_set, schedule, score_weights  # noqa: F401
 from .validate import PredictMixin, schedule as validate_schedule
 
@@ -40,225 +44,10 @@ BFGS_OPTIONS = {
 _SLOTS = ("collo", "IC", "SRC", "NB", "FIX")   # 8 floats each in the loss-sum buffer
 
 
-def _col(a):
-    return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
-
-
-def xavier_init(layers: Sequence[int], rng: np.random.Generator):
-    """initialize_NN / xavier_init (INF:141-156) as one function of a layer list and a generator: truncated normal (|z| <= 2) times
-    sqrt(2/(in+out)), zero biases of shape [1, out].  The build's own seeded stream (TF1's is
-    not reproducible).  The model classes also carry the reference's two METHODS (net_api.NetApi)."""
-    Ws, bs = [], []
-    for i in range(len(layers) - 1):
-        n_in, n_out = layers[i], layers[i + 1]
-        Ws.append(truncated_normal(rng, (n_in, n_out), float(np.sqrt(2.0 / (n_in + n_out)))))
-        bs.append(np.zeros((1, n_out), dtype=np.float32))
-    return Ws, bs
-
-
-def pack_params(weights, biases) -> np.ndarray:
-    """[W_list, b_list] -> flat fp32 vector W0,b0,W1,b1,... (the C-ABI layout)."""
-    parts = []
-    for W, b in zip(weights, biases):
-        parts += [np.asarray(W, dtype=np.float32).reshape(-1), np.asarray(b, dtype=np.float32).reshape(-1)]
-    return np.concatenate(parts)
-
-
-def unpack_params(flat, layers):
-    Ws, bs, o = [], [], 0
-    flat = np.asarray(flat)
-    for i in range(len(layers) - 1):
-        n_in, n_out = layers[i], layers[i + 1]
-        Ws.append(flat[o:o + n_in * n_out].reshape(n_in, n_out).copy())
-        o += n_in * n_out
-        bs.append(flat[o:o + n_out].reshape(1, n_out).copy())
-        o += n_out
-    assert o == flat.size
-    return Ws, bs
-
-
-def evaluate_with_finite_gradient(engine, evaluate, n_params, state, device_check=0, check=None):
-    """Run ``evaluate()`` (it fills and returns the device buffer [grad | sums]) and bring the result to the host.  The 16-bit
-    reverse pass can overflow when residuals are orders of magnitude above their trained size (include/pinn_hip.h,
-    PINN_ADJOINT_SHIFT); the sums of squares are still right then, only the gradient is non-finite.  In that case the adjoint
-    shift of the engine is raised by 4 (x1/16) and the evaluation repeated; once the loss has fallen 256-fold below where the shift
-    was raised, it is lowered again.  ``state`` is a dict the caller keeps between evaluations.  ``device_check=P``: test the first P
-    entries on the device and return only the sums behind them.  Deterministic in every rank of a
-    data-parallel job (all ranks see the same reduced buffer).  ``check``: called behind the host synchronisation of every evaluation,
-    BEFORE the result is looked at -- the model classes pass the status check of their collective (a failed P2P all-reduce leaves NaN in the
-    buffer: that must raise as a collective failure, not climb this ladder)."""
-    for _ in range(7):
-        buf = evaluate().detach()
-        if device_check:         # gradient stays on the device: check it there, bring only the loss sums back
-            finite = bool(torch.isfinite(buf[:device_check]).all())
-            if check is not None:
-                check()
-            if finite:
-                return buf[device_check:].cpu().numpy()
-        else:
-            host = buf.cpu().numpy()
-            if check is not None:
-                check()
-            if np.isfinite(host[:n_params]).all():
-                return host
-        # a weight beyond the fused kernels' format (|w| <= 2047) poisons the whole result with NaN: leave the fused path and repeat
-        leave = getattr(engine, "leave_fused_path_if_weights_out_of_range", None)
-        if leave is not None and state.get("theta") is not None and leave(state["theta"]):
-            continue
-        if engine.adjoint_shift >= 24:
-            break
-        engine.adjoint_shift = min(engine.adjoint_shift + 4, 24)
-        state["raised_at"] = None                    # filled with the loss of the next successful evaluation
-    raise FloatingPointError("non-finite gradient even with the reverse pass scaled by 2^-24")
-
-
-def relax_adjoint_shift(engine, loss, state):
-    """Companion of evaluate_with_finite_gradient: call with the loss of every successful evaluation."""
-    if engine.adjoint_shift == 0:
-        return
-    if state.get("raised_at") is None:
-        state["raised_at"] = loss
-    elif loss < state["raised_at"] / 256.0:
-        engine.adjoint_shift -= 4
-        state["raised_at"] = loss
-
-
-def all_reduce_sum(buf, group, events=None, p2p=None, adam=None, n_params=0):
-    """The step's one collective: all-reduce(sum) of the fused buffer [gradient | loss sums], enqueued in stream order behind the kernels that
-    filled it.  Default: torch.distributed.all_reduce (RCCL under the "nccl" backend).  ``p2p`` (a p2p.P2PAllReduce): the library's one-shot
-    kernel over IPC-mapped peer buffers instead; with ``adam = (params, m, v, lr, step)`` it also applies the Adam update to the first
-    ``n_params`` entries of the sum -- returns True then.  ``events``: a list that receives one (start, end) pair of timing events per call,
-    recorded on the current stream around the collective (with RCCL the stream waits for the communicator's own stream, so the pair brackets
-    it) -- bench.py's ``allreduce_ms``; None (default): nothing is recorded."""
-    if events is not None:
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        ev[0].record()
-    folded = False
-    if p2p is not None:
-        p2p.all_reduce(buf, adam=adam, n_params=n_params)
-        folded = adam is not None
-    else:
-        torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM, group=group)
-    if events is not None:
-        ev[1].record()
-        events.append(ev)
-    return folded
-
-
-def lbfgs_on_device(theta, loss_and_grad, options, callback=None):
-    """The L-BFGS stage without the host in the loop: ``torch.optim.LBFGS`` (two-loop recursion with ``maxcor`` correction pairs and a
-    strong-Wolfe line search, all vector work on the GPU in fp32) drives the same kernels.  ``loss_and_grad()`` evaluates at the current
-    ``theta`` and returns (loss as float, gradient device tensor).  scipy's L-BFGS-B -- what the reference uses through
-    ScipyOptimizerInterface -- spends ~35 ms per iteration on a 35 k-parameter net with 50 pairs, ten times the kernels' time; this is
-    the opt-in alternative (``train_bfgs(..., backend="torch")``).  The iterates differ from scipy's (another line search), the
-    objective and its gradient do not."""
-    p = theta.detach().clone().requires_grad_(True)
-    opt = torch.optim.LBFGS([p], lr=1.0, max_iter=int(options.get("maxiter", 1000)), max_eval=int(options.get("maxfun", 1250)),
-                            history_size=int(options.get("maxcor", 50)), tolerance_grad=float(options.get("gtol", 1e-10)),
-                            tolerance_change=float(options.get("tolerance_change", 1e-14)), line_search_fn="strong_wolfe")
-    stats = {"nfev": 0, "fun": None}
-
-    def closure():
-        theta.copy_(p.detach())
-        loss, grad = loss_and_grad()
-        p.grad = grad.detach().clone()
-        stats["nfev"] += 1
-        stats["fun"] = loss
-        if callback is not None:
-            callback(loss)
-        return torch.tensor(loss, dtype=torch.float32, device=theta.device)
-
-    opt.step(closure)
-    theta.copy_(p.detach())
-    final = loss_and_grad()[0]                       # the optimizer's last point is not necessarily its last evaluation
-    stats["fun"] = final
-    stats["nit"] = opt.state[p].get("n_iter", 0)
-    return stats
-
-
-BFGS_BACKENDS = ("scipy", "torch", "hip")
-
-
-def check_backend(backend):
-    if backend not in BFGS_BACKENDS:
-        raise ValueError(f"backend must be one of {BFGS_BACKENDS}, not {backend!r}")
-
-
-class LbfgsResult(dict):
-    """What a device L-BFGS stage returns: fun, nit, nfev, status, message, success -- the fields of scipy's OptimizeResult a caller of
-    train_bfgs looks at (the parameters stay on the device, in the model's theta)."""
-    __getattr__ = dict.get
-
-
-_LBFGS_MESSAGES = {1: "CONVERGENCE: max|g| <= gtol", 2: "CONVERGENCE: relative reduction of f <= ftol", 3: "STOP: total no. of iterations reached limit",
-                   4: "STOP: total no. of f and g evaluations reached limit", 5: "ABNORMAL: line search failed",
-                   6: "ABNORMAL: loss or gradient not finite at the start point", 7: "ABNORMAL: gradient not finite at an acceptable point"}
-
-
-def lbfgs_hip(engine, theta, evaluate, n_params, loss_coeffs, options, callback=None, grad_scale=1.0, loss_scale=1.0, block=16, check=None,
-              shift_state=None, ladder=True, what="this stage"):
-    """The L-BFGS stage as a stream of kernels (``backend="hip"``): the library's own optimizer (pinn_lbfgs_*, include/pinn_hip.h: compact-form
-    direction, strong-Wolfe line search and scipy's stop rules, all on the device) behind the same loss kernels.  ``evaluate()`` enqueues the
-    loss + gradient kernels at ``theta`` and returns the device buffer [grad (n_params) | sums]; the loss the optimizer sees is
-    ``sum_j loss_coeffs[j] * sums[j]`` and its gradient ``grad_scale * grad``.  Nothing synchronises per evaluation: *evaluate -> advance* is
-    enqueued in blocks of ``block`` evaluations (``options["block"]`` overrides), the status is read ONCE per block, and the block's losses come
-    out of the device's loss ring -- so ``callback(loss / loss_scale)`` still fires once per evaluation, in order, but in BATCHES of up to
-    ``block`` calls, after the block has run.  When the status says stop, nothing more is enqueued (the calls of a block that were already behind
-    the stop change nothing); ``theta`` then holds the last accepted point, which is the best one.  ``check``: called at every status read (the
-    model classes pass their collective's status check).  A stop with a non-finite gradient climbs the range ladder of
-    evaluate_with_finite_gradient (leave the fused path for an out-of-range weight, else adjoint shift + 4) and starts again from the last
-    accepted point with an empty history and what is left of maxiter / maxfun; with ``shift_state`` (the model's bookkeeping dict) the shift is
-    lowered again as the loss falls (relax_adjoint_shift, at every status read -- once per block instead of once per evaluation).
-    ``ladder=False``: the evaluation has no range ladder (the plate's pre-training losses ignore the adjoint shift): a non-finite loss or gradient
-    raises FloatingPointError at once, naming ``what``.  Returns an LbfgsResult (fun, nit, nfev, status, message)."""
-    opts = dict(options)
-    block = max(1, min(int(opts.pop("block", block)), 1024))
-    maxfun, maxiter = int(opts.get("maxfun", 15000)), int(opts.get("maxiter", 15000))
-    opts.setdefault("gtol", 1e-5)                        # scipy's default pgtol (the reference does not set it)
-    state = engine.lbfgs_state(n_params, int(opts.get("maxcor", 10)))
-    nfev = nit = 0
-    while True:
-        engine.lbfgs_init(state, dict(opts, maxfun=max(1, maxfun - nfev), maxiter=max(0, maxiter - nit)), loss_coeffs, grad_scale)
-        seen = 0
-        while True:
-            for _ in range(max(1, min(block, maxfun - nfev - seen))):
-                buf = evaluate()
-                engine.lbfgs_advance(state, theta, buf[:n_params], buf[n_params:])
-            rec = engine.lbfgs_status(state)
-            if check is not None:
-                check()
-            if callback is not None:
-                for f in engine.lbfgs_losses(state, seen, rec["loss_pos"] - seen):
-                    callback(f / loss_scale)
-            seen = rec["loss_pos"]
-            if shift_state is not None and np.isfinite(rec["f"]):
-                relax_adjoint_shift(engine, rec["f"] / loss_scale, shift_state)
-            if rec["status"] != 0:
-                break
-        nfev += rec["evaluations"]
-        nit += rec["iterations"]
-        if rec["status"] in (6, 7) and not ladder:
-            raise FloatingPointError(f"{what} produced a non-finite loss or gradient (loss = {rec['f'] / loss_scale}); "
-                                     f"restart from other weights or use precision='bf16x3'")
-        if rec["status"] in (6, 7):
-            leave = getattr(engine, "leave_fused_path_if_weights_out_of_range", None)
-            if leave is not None and leave(theta):
-                pass
-            elif engine.adjoint_shift < 24:
-                engine.adjoint_shift = min(engine.adjoint_shift + 4, 24)
-                if shift_state is not None:
-                    shift_state["raised_at"] = None
-            else:
-                raise FloatingPointError("non-finite loss or gradient even with the reverse pass scaled by 2^-24")
-            if nfev < maxfun:
-                continue
-        break
-    return LbfgsResult(fun=rec["f"], nit=nit, nfev=nfev, status=rec["status"], message=_LBFGS_MESSAGES.get(rec["status"], "?"),
-                       success=rec["status"] in (1, 2), max_abs_grad=rec["max_abs_grad"], pairs=rec["pairs"], skipped=rec["skipped"])
-
-
-class DeepHPM(NetApi, PredictMixin):
+class DeepHPM(ShardedSetsModel, PredictMixin):
     """Drop-in for the reference's model class on the wave cases (INF:21-376)."""
+    N_IN, COLLO_NAMES = 3, ("x_c", "y_c", "t_c")
+    COLLO_TERMS, SUMS_STRIDE, SLOTS = (4, 3), 8, _SLOTS
 
     def __init__(self, Collo, SRC, IC, UP, uv_layers, lb, ub, ExistModel=0, modelDir='', *, case="infinite",
                  FIX=None, precision="f16x3", engine=None, seed=1111, process_group=None, verbose=True,
@@ -276,131 +65,21 @@ class DeepHPM(NetApi, PredictMixin):
         self.uv_layers = [int(v) for v in uv_layers]
         self.verbose = verbose
 
-        # ---- data parallel topology
-        self.pg = process_group
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            self.rank = torch.distributed.get_rank(self.pg)
-            self.world = torch.distributed.get_world_size(self.pg)
-        else:
-            self.rank, self.world = 0, 1
-        if shard_as is not None:
-            # ``shard_as=(r, w)``: hold and evaluate rank r's share of a w-rank job WITHOUT the other ranks -- every set sharded by _shard, sums
-            # weighted with the global 1/N, exactly what that rank executes per step (bench.py --rank-share; the collective is a separate switch)
-            self.rank, self.world = int(shard_as[0]), int(shard_as[1])
-        # ``always_reduce``: run the step's all-reduce even in a process group of one rank -- the collective branch (RCCL under the
-        # "nccl" backend) then executes on a single GPU exactly as it does on eight, which is how the tests prove that path here
-        self._reduce = (self.world > 1 and shard_as is None) or (bool(always_reduce) and torch.distributed.is_available() and torch.distributed.is_initialized())
-
-        # ---- engine (GPU kernels); tests may inject a stand-in with the same methods
-        if engine is None:
-            from .hip_engine import HipEngine
-            n_max = max(int(np.asarray(Collo).shape[0]) // self.world + 1, 1 << 14)
-            engine = HipEngine(self.uv_layers, precision=precision, max_points=n_max)
-        self.engine = engine
-        self.device = engine.device
-        if hasattr(engine, "warn_if_slow_path"):
-            engine.warn_if_slow_path("wave")      # no silent slow path: a depth the fused kernel is not compiled for says so once
-
-        # ---- weights (INF:64-68)
-        self._init_rng = np.random.default_rng(seed)
-        if ExistModel == 0:
-            W, b = self.initialize_NN(self.uv_layers)
-        else:
-            W, b = self.load_NN(modelDir, self.uv_layers)
-        self.n_params = sum(w.size for w in W) + sum(x.size for x in b)
-        self.theta = torch.from_numpy(pack_params(W, b)).to(self.device)
-        self._shift_state["theta"] = self.theta        # (updated in place: the weight-range check of evaluate_with_finite_gradient reads it)
-        self.adam_m = torch.zeros_like(self.theta)
-        self.adam_v = torch.zeros_like(self.theta)
-        self.adam_t = 0
+        self._init_topology(process_group, always_reduce, shard_as)
+        # engine (GPU kernels); tests may inject a stand-in with the same methods
+        self._set_engine(self._default_engine(self.uv_layers, precision, np.asarray(Collo).shape[0]) if engine is None else engine, "wave")
+        self._init_net(seed, ExistModel, modelDir)
 
         # ---- point sets, column split like INF:40-59, stored SoA on the device
-        def dev(a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
-
-        Collo = np.asarray(Collo, dtype=np.float64)
-        self.x_c, self.y_c, self.t_c = Collo[:, 0:1], Collo[:, 1:2], Collo[:, 2:3]      # host copies, as the reference keeps them (INF:40-42)
-        # Device residency: one process holds the whole set; a data-parallel rank holds only ITS rows of each collocation block
-        # (uploaded when a block is first used, see _rows), so device memory and upload time scale with 1/world.
-        self._n_collo = Collo.shape[0]
-        self._collo_host = tuple(np.ascontiguousarray(_col(Collo[:, k]), dtype=np.float32) for k in range(3))
-        self._collo_full = tuple(dev(a) for a in self._collo_host) if self.world == 1 else None
-        self._collo_cache = {}
-        self._sides = {}      # name -> (x, y, t, targets[7,n] or None, out columns)
-
-        def side(name, A, cols, target_cols=None):
-            if A is None:
-                return
-            A = np.asarray(A, dtype=np.float64)
-            if A.shape[0] == 0:
-                return
-            n_glob = A.shape[0]
-            s, e = self._shard(0, n_glob)            # this rank's contiguous rows
-            A = A[s:e]
-            tg = None
-            if target_cols is not None and e > s:
-                T = np.zeros((7, A.shape[0]), dtype=np.float32)
-                for o, cidx in zip(cols, target_cols):
-                    T[o] = A[:, cidx]
-                tg = dev(T)
-            self._sides[name] = (dev(_col(A[:, 0])), dev(_col(A[:, 1])), dev(_col(A[:, 2])), tg, tuple(cols), n_glob)
-
-        side("IC", IC, (0, 1, 2, 3))                     # u,v,ut,vt = 0 at t=0          INF:111-114
-        side("SRC", SRC, (0, 1), (3, 4))                 # u,v = source displacement     INF:115-116
-        side("NB", UP, (5, 6))                           # s22,s12 = 0 on the free edge  INF:117-118
-        side("FIX", FIX, (0, 1))                         # u,v = 0 on the fixed edges    CONF:145-146
+        self._init_collocation(Collo)
+        self._add_side("IC", IC, (0, 1, 2, 3))                     # u,v,ut,vt = 0 at t=0          INF:111-114
+        self._add_side("SRC", SRC, (0, 1), (3, 4))                 # u,v = source displacement     INF:115-116
+        self._add_side("NB", UP, (5, 6))                           # s22,s12 = 0 on the free edge  INF:117-118
+        self._add_side("FIX", FIX, (0, 1))                         # u,v = 0 on the fixed edges    CONF:145-146
         self.SRC, self.IC, self.UP, self.FIX = SRC, IC, UP, FIX
 
-        P = self.n_params
-        self._buf = torch.zeros(P + 8 * len(_SLOTS), dtype=torch.float32, device=self.device)
-        # ``collective``: "rccl" (default) = torch.distributed.all_reduce of the fused buffer; "p2p" = the library's one-shot all-reduce over
-        # IPC-mapped peer buffers with the Adam update in the same kernel (p2p.P2PAllReduce, include/pinn_hip.h: pinn_p2p_*)
-        if collective not in ("rccl", "p2p"):
-            raise ValueError("collective must be 'rccl' or 'p2p'")
-        self._p2p = None
-        if collective == "p2p" and self._reduce:
-            if not hasattr(self.engine, "lib"):
-                raise ValueError("collective='p2p' needs the HIP engine (the one-shot all-reduce is a kernel of libpinn_hip.so)")
-            from .p2p import P2PAllReduce
-            self._p2p = P2PAllReduce(self.engine.lib, self._buf.numel(), self.pg, timeout_s=p2p_timeout_s)
-
-    def _check_collective(self):
-        """collective='p2p': raise if a one-shot all-reduce has failed on this rank (p2p.P2PAllReduce.check: reads a host word, no
-        synchronisation) -- called behind every host sync point of train / train_bfgs / getloss, so that a rank that missed a call, or whose
-        peer did, stops at once instead of training on with diverged parameters (round-5 review)."""
-        if getattr(self, "_p2p", None) is not None:
-            self._p2p.check()
-
-    def close(self):
-        """Release the P2P communicator (collective: every rank calls it).  Nothing to do for collective='rccl'."""
-        p2p, self._p2p = getattr(self, "_p2p", None), None
-        if p2p is not None:
-            p2p.close()
-
-    # ------------------------------------------------------------------------------------------
-    # checkpoints: the reference's [W_list, b_list] pickle (INF:159-186); .npz is accepted too
-    # ------------------------------------------------------------------------------------------
-    def save_NN(self, fileDir, TYPE=''):
-        """INF:159-170.  A name ending in ``.npz`` writes plain arrays (the documented default of this package); any other name writes the
-        reference's pickle of [W_list, b_list] (net_api.py)."""
-        W, b = unpack_params(self.theta.detach().cpu().numpy(), self.uv_layers)
-        write_checkpoint(fileDir, W, b, self.uv_layers)
-        if self.verbose:
-            print("Save NN parameters successfully...")
-
-    def load_NN(self, fileDir, layers):
-        """INF:172-186: ``.npz`` or the reference's pickle (read by an arrays-only unpickler, net_api.py)"""
-        num_layers = len(layers)
-        uv_weights, uv_biases = read_checkpoint(fileDir)
-        # Stored model must have the same number of layers (INF:178)
-        assert num_layers == (len(uv_weights) + 1)
-        weights = [np.asarray(w, dtype=np.float32) for w in uv_weights]
-        biases = [np.asarray(b, dtype=np.float32).reshape(1, -1) for b in uv_biases]
-        for i, w in enumerate(weights):
-            assert w.shape == (layers[i], layers[i + 1]), "stored weight shape does not match uv_layers"
-        if self.verbose:
-            print("Load NN parameters successfully...")
-        return weights, biases
+        self._buf = torch.zeros(self.n_params + 8 * len(_SLOTS), dtype=torch.float32, device=self.device)
+        self._init_collective(collective, p2p_timeout_s)
 
     def set_weights(self, weights, biases):
         self.theta.copy_(torch.from_numpy(pack_params(weights, biases)).to(self.device))
@@ -409,19 +88,12 @@ class DeepHPM(NetApi, PredictMixin):
     # graph pieces as callables on column arrays [N,1] (INF:188-276)
     # ------------------------------------------------------------------------------------------
     def _fields(self, x, y, t):
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, t)]
+        xs = self._device_columns((x, y, t))
         return self.engine.fields(self.theta, xs[0], xs[1], xs[2], self.lb, self.ub, self.normalize)   # [4,7,N]
 
-    @staticmethod
-    def _cols(T):
-        return tuple(T[i].detach().cpu().numpy().reshape(-1, 1) for i in range(T.shape[0]))
-
-    # neural_net(X, weights, biases): net_api.NetApi, through these two
-    def _current_theta(self):
-        return self.theta
-
+    # neural_net(X, weights, biases): net_api.NetApi, through _current_theta and this
     def _net_fields(self, eng, theta, X):
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(X[:, k]), dtype=np.float32)).to(eng.device) for k in range(3)]
+        xs = self._device_columns((X[:, k] for k in range(3)), eng.device)
         return eng.fields(theta, xs[0], xs[1], xs[2], self.lb, self.ub, self.normalize)[0]
 
     def net_uv(self, x, y, t):                       # INF:201-211
@@ -470,7 +142,7 @@ class DeepHPM(NetApi, PredictMixin):
     def residual_score(self, x, y, t, weights=None):
         """sum_i weights[i] * f_i^2 of net_f_sig's seven residuals (INF:221-265) per point, numpy [N,1], formed on the device: the measure
         refine_collocation ranks by.  Default ``weights``: what the case's loss layout puts on the collocation terms."""
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, t)]
+        xs = self._device_columns((x, y, t))
         return self._score_device(xs, self._score_weights(weights)).detach().cpu().numpy().reshape(-1, 1)
 
     def refine_collocation(self, candidates, n_replace, weights=None, *, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
@@ -505,33 +177,6 @@ class DeepHPM(NetApi, PredictMixin):
     # ------------------------------------------------------------------------------------------
     # one evaluation of loss terms + total gradient on one collocation block
     # ------------------------------------------------------------------------------------------
-    def _shard(self, lo, hi):
-        n = hi - lo
-        return lo + n * self.rank // self.world, lo + n * (self.rank + 1) // self.world
-
-    def _rows(self, lo, hi):
-        """Device tensors (x, y, t) of THIS rank's rows of the collocation block [lo, hi)."""
-        s, e = self._shard(lo, hi)
-        if self._collo_full is not None:
-            return tuple(a[s:e] for a in self._collo_full)
-        key = (lo, hi)
-        if key in self._collo_cache:
-            self._collo_cache[key] = self._collo_cache.pop(key)          # most recently used last
-        else:
-            # Bounded cache, least recently used out first: TWICE this rank's share of the set stays resident, so that train() walking
-            # its blocks and getloss() asking for (0, N) in between -- two batchings of the same rows -- alternate without re-uploading
-            # a shard from the host every time, and shifting windows still cannot grow the device footprint beyond that bound.
-            self._collo_cache[key] = tuple(torch.from_numpy(h[s:e]).to(self.device) for h in self._collo_host)
-            cap = 2 * (-(-self._n_collo // self.world)) + 64
-            while len(self._collo_cache) > 1 and sum(v[0].numel() for v in self._collo_cache.values()) > cap:
-                del self._collo_cache[next(iter(self._collo_cache))]
-        return self._collo_cache[key]
-
-    @property
-    def _collo(self):
-        """this rank's rows of the whole collocation set"""
-        return self._rows(0, self._n_collo)
-
     def _loss_and_grad(self, idx_start, idx_end, sums_out=None, adam=None):
         """Fills self._buf = [grad (P) | 8 floats per slot] with this rank's partial sums, then
         all-reduces.  Everything stays on the device.  Single process only: ``sums_out`` (a view of
@@ -606,31 +251,6 @@ class DeepHPM(NetApi, PredictMixin):
                                      (self.theta, self.adam_m, self.adam_v, adam[0], adam[1]) if fold else None, P)
         return stepped
 
-    def _terms_from_sums(self, sums, n_blk):
-        """sums: [len(_SLOTS), 8] numpy array of sums of squares -> the reference's loss terms."""
-        lay = self.layout
-        out = {"loss_f_uv": float(sums[0, :4].sum() / n_blk), "loss_f_s": float(sums[0, 4:7].sum() / n_blk)}
-        for k, name in enumerate(_SLOTS[1:], start=1):
-            if name in self._sides:
-                n = self._sides[name][5]
-                cols = list(self._sides[name][4])
-                out["loss_" + name] = float(sums[k, cols].sum() / n)
-            else:
-                out["loss_" + name] = 0.0
-        out["loss"] = (lay["f_uv"] * out["loss_f_uv"] + lay["f_s"] * out["loss_f_s"] + lay["IC"] * out["loss_IC"]
-                       + lay["SRC"] * out["loss_SRC"] + lay["NB"] * out["loss_NB"] + lay["FIX"] * out["loss_FIX"])
-        return out
-
-    def _loss_coeffs(self, n_blk):
-        """_terms_from_sums(...)["loss"] as a coefficient vector over the sums buffer (8 floats per slot): the loss is linear in it"""
-        lay = self.layout
-        c = np.zeros((len(_SLOTS), 8))
-        c[0, :4], c[0, 4:7] = lay["f_uv"] / n_blk, lay["f_s"] / n_blk
-        for k, name in enumerate(_SLOTS[1:], start=1):
-            if name in self._sides:
-                c[k, list(self._sides[name][4])] = lay[name] / self._sides[name][5]
-        return c.reshape(-1).tolist()
-
     # ------------------------------------------------------------------------------------------
     # training drivers
     # ------------------------------------------------------------------------------------------
@@ -660,10 +280,8 @@ class DeepHPM(NetApi, PredictMixin):
                 self._loss_and_grad(idx_start, idx_end)
                 return self._buf
 
-            if iter > 0 and getattr(self.engine, "needs_finite_probe", False) and not self._shift_state.get("probed"):
-                # once per model: a synchronous evaluation settles the adjoint shift (Adam's steps are small, it rarely moves after)
-                evaluate_with_finite_gradient(self.engine, probe, P, self._shift_state, check=self._check_collective)
-                self._shift_state["probed"] = True
+            if iter > 0:
+                self._settle_adjoint_shift(self.engine, probe, P)
             for it in range(iter):
                 self.adam_t += 1
                 updated = self._loss_and_grad(idx_start, idx_end, sums_out=rec[it], adam=(learning_rate, self.adam_t))     # (sums_out: one launch less per step than copying afterwards)
@@ -706,7 +324,6 @@ class DeepHPM(NetApi, PredictMixin):
         optimizer on the device as well (lbfgs_on_device), for when the host update is the bottleneck.  ``backend="hip"``: the library's own
         L-BFGS (lbfgs_hip): no host round trip per evaluation, the callbacks arrive in batches.  Any other name raises ValueError."""
         check_backend(backend)
-        P = self.n_params
         opts = dict(BFGS_OPTIONS[self.case])
         if options:
             opts.update(options)
@@ -720,30 +337,9 @@ class DeepHPM(NetApi, PredictMixin):
                 self._loss_and_grad(idx_start, idx_end)
                 return self._buf
 
-            def fun(theta64):
-                self.theta.copy_(torch.from_numpy(theta64.astype(np.float32)).to(self.device))
-                host = evaluate_with_finite_gradient(self.engine, evaluate, P, self._shift_state, check=self._check_collective)
-                tm = self._terms_from_sums(host[P:].reshape(len(_SLOTS), 8), idx_end - idx_start)
-                relax_adjoint_shift(self.engine, tm["loss"], self._shift_state)
-                self.callback(tm["loss"])
-                return tm["loss"], host[:P].astype(np.float64)
-
-            if backend == "torch":
-                def loss_and_grad():
-                    host = evaluate_with_finite_gradient(self.engine, evaluate, 0, self._shift_state, device_check=P, check=self._check_collective)
-                    tm = self._terms_from_sums(host.reshape(len(_SLOTS), 8), idx_end - idx_start)
-                    relax_adjoint_shift(self.engine, tm["loss"], self._shift_state)
-                    return tm["loss"], self._buf[:P]
-                result = lbfgs_on_device(self.theta, loss_and_grad, opts, self.callback)
-                continue
-            if backend == "hip":
-                result = lbfgs_hip(self.engine, self.theta, evaluate, P, self._loss_coeffs(idx_end - idx_start), opts, self.callback,
-                                   check=self._check_collective, shift_state=self._shift_state)
-                continue
-            import scipy.optimize
-            x0 = self.theta.detach().cpu().numpy().astype(np.float64)
-            result = scipy.optimize.minimize(fun, x0, jac=True, method='L-BFGS-B', options=opts)
-            self.theta.copy_(torch.from_numpy(result.x.astype(np.float32)).to(self.device))
+            result = self._lbfgs_stage(backend, self.engine, self.theta, evaluate,
+                                       lambda sums: self._terms_from_sums(sums.reshape(len(_SLOTS), 8), idx_end - idx_start)["loss"],
+                                       self._loss_coeffs(idx_end - idx_start), opts)
         return result
 
     # ------------------------------------------------------------------------------------------
@@ -825,5 +421,7 @@ class DeepHPMConfined(DeepHPM):
         """CONF:453-472: (loss, loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss_FIX) on the full sets."""
         n = self._n_collo
         self._loss_and_grad(0, n)
-        tm = self._terms_from_sums(self._buf[self.n_params:].detach().cpu().numpy().reshape(len(_SLOTS), 8), n)
+        host = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(_SLOTS), 8)
+        self._check_collective()
+        tm = self._terms_from_sums(host, n)
         return tm["loss"], tm["loss_f_uv"], tm["loss_f_s"], tm["loss_IC"], tm["loss_SRC"], tm["loss_FIX"]

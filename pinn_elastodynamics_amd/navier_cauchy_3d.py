@@ -17,8 +17,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, unpack_params, xavier_init  # noqa: F401
-from .net_api import NetApi, read_checkpoint, write_checkpoint
+from .model_base import ShardedSetsModel
+from .optim import all_reduce_sum, check_backend
 from .refine import Candidates, refine_sharded_set, schedule, score_weights
 
 OUT = ("u", "v", "w", "ut", "vt", "wt", "s11", "s22", "s33", "s12", "s13", "s23")
@@ -26,12 +26,14 @@ _SLOTS = ("collo", "IC", "SRC", "NB")          # 16 floats each in the loss-sum 
 LOSS_LAYOUT_3D = dict(f_uv=5.0, f_s=5.0, IC=2.0, SRC=2.0, NB=2.0)        # the semi-infinite script's weights (SEMI:127)
 
 
-class NavierCauchy3D(NetApi):
+class NavierCauchy3D(ShardedSetsModel):
     """NavierCauchy3D(Collo[N,4], SRC[Ns,7], IC[Ni,4], TOP[Nt,4], uv_layers, lb[4], ub[4], ExistModel=0, modelDir='')
 
     Collo: collocation points (x, y, z, t); SRC: points with prescribed displacement (x, y, z, t, u, v, w) -- the source;
     IC: points at t = 0 where u, v, w, ut, vt, wt vanish; TOP: points on the free surface z = ub[2] where s33 = s13 = s23 = 0.
     uv_layers = [4] + depth * [width] + [12]."""
+    N_IN, COLLO_NAMES = 4, ("x_c", "y_c", "z_c", "t_c")
+    COLLO_TERMS, SUMS_STRIDE, SLOTS = (6, 6), 16, _SLOTS
 
     def __init__(self, Collo, SRC, IC, TOP, uv_layers, lb, ub, ExistModel=0, modelDir='', *, precision="f16x3", engine=None, seed=1111,
                  process_group=None, verbose=True, E=2.5, mu=0.25, rho=1.0, normalize=True, layout: Optional[dict] = None,
@@ -48,117 +50,25 @@ class NavierCauchy3D(NetApi):
         self.uv_layers = [int(v) for v in uv_layers]
         assert self.uv_layers[0] == 4 and self.uv_layers[-1] == 12, "uv_layers = [4] + depth*[width] + [12]"
         self.verbose = verbose
-        self.pg = process_group
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            self.rank = torch.distributed.get_rank(self.pg)
-            self.world = torch.distributed.get_world_size(self.pg)
-        else:
-            self.rank, self.world = 0, 1
-        # (always_reduce: the collective branch also at one rank -- see elastic_wave.DeepHPM)
-        self._reduce = self.world > 1 or (bool(always_reduce) and torch.distributed.is_available() and torch.distributed.is_initialized())
-        if engine is None:
-            from .hip_engine import HipEngine
-            n_max = max(int(np.asarray(Collo).shape[0]) // self.world + 1, 1 << 14)
-            engine = HipEngine(self.uv_layers, precision=precision, max_points=n_max)
-        self.engine = engine
-        self.device = engine.device
-        if hasattr(engine, "warn_if_slow_path"):
-            engine.warn_if_slow_path("nc3d")
-        self._init_rng = np.random.default_rng(seed)
-        if ExistModel == 0:
-            W, b = self.initialize_NN(self.uv_layers)
-        else:
-            W, b = self.load_NN(modelDir, self.uv_layers)
-        self.n_params = sum(w.size for w in W) + sum(x.size for x in b)
-        self.theta = torch.from_numpy(pack_params(W, b)).to(self.device)
-        self._shift_state["theta"] = self.theta
-        self.adam_m = torch.zeros_like(self.theta)
-        self.adam_v = torch.zeros_like(self.theta)
-        self.adam_t = 0
-
-        def dev(a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
-
-        Collo = np.asarray(Collo, dtype=np.float64)
-        self.x_c, self.y_c, self.z_c, self.t_c = (Collo[:, k:k + 1] for k in range(4))
-        self._n_collo = Collo.shape[0]
-        self._collo_host = tuple(np.ascontiguousarray(_col(Collo[:, k]), dtype=np.float32) for k in range(4))
-        self._collo_full = tuple(dev(a) for a in self._collo_host) if self.world == 1 else None
-        self._collo_cache = {}
-        self._sides = {}
-
-        def side(name, A, cols, target_cols=None):
-            if A is None:
-                return
-            A = np.asarray(A, dtype=np.float64)
-            if A.shape[0] == 0:
-                return
-            n_glob = A.shape[0]
-            s, e = self._shard(0, n_glob)
-            A = A[s:e]
-            tg = None
-            if target_cols is not None and e > s:
-                T = np.zeros((12, A.shape[0]), dtype=np.float32)
-                for o, cidx in zip(cols, target_cols):
-                    T[o] = A[:, cidx]
-                tg = dev(T)
-            self._sides[name] = tuple(dev(_col(A[:, k])) for k in range(4)) + (tg, tuple(cols), n_glob)
-
-        side("IC", IC, (0, 1, 2, 3, 4, 5))                 # u, v, w, ut, vt, wt = 0 at t = 0      (as SEMI:119-122)
-        side("SRC", SRC, (0, 1, 2), (4, 5, 6))             # prescribed source displacement       (as SEMI:123-124)
-        side("NB", TOP, (8, 10, 11))                       # s33 = s13 = s23 = 0 on the free top  (as SEMI:125-126)
+        self._init_topology(process_group, always_reduce)
+        self._set_engine(self._default_engine(self.uv_layers, precision, np.asarray(Collo).shape[0]) if engine is None else engine, "nc3d")
+        self._init_net(seed, ExistModel, modelDir)
+        self._init_collocation(Collo)
+        self._add_side("IC", IC, (0, 1, 2, 3, 4, 5))                 # u, v, w, ut, vt, wt = 0 at t = 0      (as SEMI:119-122)
+        self._add_side("SRC", SRC, (0, 1, 2), (4, 5, 6))             # prescribed source displacement       (as SEMI:123-124)
+        self._add_side("NB", TOP, (8, 10, 11))                       # s33 = s13 = s23 = 0 on the free top  (as SEMI:125-126)
         self.SRC, self.IC, self.TOP = SRC, IC, TOP
         self._buf = torch.zeros(self.n_params + 16 * len(_SLOTS), dtype=torch.float32, device=self.device)
-        # collective: "rccl" (torch.distributed.all_reduce) or "p2p" (the library's one-shot all-reduce over IPC-mapped peer buffers; elastic_wave.DeepHPM)
-        if collective not in ("rccl", "p2p"):
-            raise ValueError("collective must be 'rccl' or 'p2p'")
-        self._p2p = None
-        if collective == "p2p" and self._reduce:
-            if not hasattr(self.engine, "lib"):
-                raise ValueError("collective='p2p' needs the HIP engine")
-            from .p2p import P2PAllReduce
-            self._p2p = P2PAllReduce(self.engine.lib, self._buf.numel(), self.pg, timeout_s=p2p_timeout_s)
-
-    def _check_collective(self):
-        """collective='p2p': raise if a one-shot all-reduce has failed on this rank (elastic_wave.DeepHPM._check_collective)"""
-        if getattr(self, "_p2p", None) is not None:
-            self._p2p.check()
-
-    def close(self):
-        """Release the P2P communicator (collective: every rank calls it).  Nothing to do for collective='rccl'."""
-        p2p, self._p2p = getattr(self, "_p2p", None), None
-        if p2p is not None:
-            p2p.close()
-
-    # ---- checkpoints: the reference's [W_list, b_list] pickle / npz (INF:159-186) ---------------------------------
-    def save_NN(self, fileDir, TYPE=''):
-        W, b = unpack_params(self.theta.detach().cpu().numpy(), self.uv_layers)
-        write_checkpoint(fileDir, W, b, self.uv_layers)        # .npz: plain arrays (documented default); otherwise the reference's pickle
-
-    def load_NN(self, fileDir, layers):
-        W, b = read_checkpoint(fileDir)                        # .npz, or the reference's pickle through the arrays-only unpickler
-        assert len(layers) == len(W) + 1                   # INF:178
-        W = [np.asarray(w, dtype=np.float32) for w in W]
-        b = [np.asarray(x, dtype=np.float32).reshape(1, -1) for x in b]
-        for i, w in enumerate(W):
-            assert w.shape == (layers[i], layers[i + 1]), "stored weight shape does not match uv_layers"
-        return W, b
+        self._init_collective(collective, p2p_timeout_s)
 
     # ---- graph pieces on column arrays [N,1] ---------------------------------------------------------------------------
     def _fields(self, x, y, z, t):
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, z, t)]
+        xs = self._device_columns((x, y, z, t))
         return self.engine.nc3d_fields(self.theta, *xs, self.lb, self.ub, self.normalize)        # [5, 12, N]
 
-    @staticmethod
-    def _cols(T):
-        return tuple(T[i].detach().cpu().numpy().reshape(-1, 1) for i in range(T.shape[0]))
-
-    # neural_net(X, weights, biases): net_api.NetApi, through these two
-    def _current_theta(self):
-        return self.theta
-
+    # neural_net(X, weights, biases): net_api.NetApi, through _current_theta and this
     def _net_fields(self, eng, theta, X):
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(X[:, k]), dtype=np.float32)).to(eng.device) for k in range(4)]
+        xs = self._device_columns((X[:, k] for k in range(4)), eng.device)
         return eng.nc3d_fields(theta, *xs, self.lb, self.ub, self.normalize)[0]
 
     def net_uv(self, x, y, z, t):
@@ -203,7 +113,7 @@ class NavierCauchy3D(NetApi):
     def residual_score(self, x, y, z, t, weights=None):
         """sum_i weights[i] * f_i^2 of net_f_sig's twelve residuals per point, numpy [N,1], formed on the device: the measure
         refine_collocation ranks by.  Default ``weights``: what the loss layout puts on the collocation terms."""
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, z, t)]
+        xs = self._device_columns((x, y, z, t))
         return self._score_device(xs, self._score_weights(weights)).detach().cpu().numpy().reshape(-1, 1)
 
     def refine_collocation(self, candidates, n_replace, weights=None, *, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
@@ -230,27 +140,6 @@ class NavierCauchy3D(NetApi):
             print('{} th iterations, Loss: {}'.format(self.count, loss))
 
     # ---- loss + gradient of one collocation block -----------------------------------------------------------------------
-    def _shard(self, lo, hi):
-        n = hi - lo
-        return lo + n * self.rank // self.world, lo + n * (self.rank + 1) // self.world
-
-    def _rows(self, lo, hi):
-        s, e = self._shard(lo, hi)
-        if self._collo_full is not None:
-            return tuple(a[s:e] for a in self._collo_full)
-        key = (lo, hi)
-        if key in self._collo_cache:
-            self._collo_cache[key] = self._collo_cache.pop(key)          # most recently used last
-        else:
-            # Bounded cache, least recently used out first: TWICE this rank's share of the set stays resident, so that train() walking
-            # its blocks and getloss() asking for (0, N) in between -- two batchings of the same rows -- alternate without re-uploading
-            # a shard from the host every time, and shifting windows still cannot grow the device footprint beyond that bound.
-            self._collo_cache[key] = tuple(torch.from_numpy(h[s:e]).to(self.device) for h in self._collo_host)
-            cap = 2 * (-(-self._n_collo // self.world)) + 64
-            while len(self._collo_cache) > 1 and sum(v[0].numel() for v in self._collo_cache.values()) > cap:
-                del self._collo_cache[next(iter(self._collo_cache))]
-        return self._collo_cache[key]
-
     def _loss_and_grad(self, idx_start, idx_end):
         """self._buf = [grad (P) | 16 floats per slot], this rank's partial sums, then all-reduced."""
         P, lay, eng, buf = self.n_params, self.layout, self.engine, self._buf
@@ -283,19 +172,6 @@ class NavierCauchy3D(NetApi):
         if self._reduce:
             all_reduce_sum(buf, self.pg, getattr(self, "collective_events", None), getattr(self, "_p2p", None))
 
-    def _terms_from_sums(self, sums, n_blk):
-        lay = self.layout
-        out = {"loss_f_uv": float(sums[0, :6].sum() / n_blk), "loss_f_s": float(sums[0, 6:12].sum() / n_blk)}
-        for k, name in enumerate(_SLOTS[1:], start=1):
-            if name in self._sides:
-                cols, n = list(self._sides[name][5]), self._sides[name][6]
-                out["loss_" + name] = float(sums[k, cols].sum() / n)
-            else:
-                out["loss_" + name] = 0.0
-        out["loss"] = (lay["f_uv"] * out["loss_f_uv"] + lay["f_s"] * out["loss_f_s"] + lay["IC"] * out["loss_IC"]
-                       + lay["SRC"] * out["loss_SRC"] + lay["NB"] * out["loss_NB"])
-        return out
-
     # ---- training drivers ---------------------------------------------------------------------------------------------
     def train(self, iter, learning_rate, batch_num, refine=None):
         """Adam loop with the reference's block-sequential batching (SEMI:290-328): returns the per-step lists
@@ -312,9 +188,8 @@ class NavierCauchy3D(NetApi):
                 self._loss_and_grad(lo, hi)
                 return self._buf
 
-            if iter > 0 and getattr(self.engine, "needs_finite_probe", False) and not self._shift_state.get("probed"):
-                evaluate_with_finite_gradient(self.engine, probe, P, self._shift_state, check=self._check_collective)
-                self._shift_state["probed"] = True
+            if iter > 0:
+                self._settle_adjoint_shift(self.engine, probe, P)
             for it in range(iter):
                 self._loss_and_grad(lo, hi)
                 rec[it].copy_(self._buf[P:])
@@ -323,32 +198,22 @@ class NavierCauchy3D(NetApi):
                 if sched is not None:
                     step += 1
                     sched.after_step(step)
-            if iter > 0 and not bool(torch.isfinite(self.theta).all()):
-                raise FloatingPointError("parameters became non-finite during train(): lower the learning rate or raise engine.adjoint_shift")
             sums = rec.detach().cpu().numpy().reshape(iter, L, 16)
             self._check_collective()                 # (behind the block's one host synchronisation)
+            if iter > 0 and not bool(torch.isfinite(self.theta).all()):
+                raise FloatingPointError("parameters became non-finite during train(): lower the learning rate or raise engine.adjoint_shift")
             for it in range(iter):
                 tm = self._terms_from_sums(sums[it], hi - lo)
                 for lst, key in zip(hist, ("loss_f_uv", "loss_f_s", "loss_IC", "loss_SRC", "loss")):
                     lst.append(tm[key])
         return hist
 
-    def _loss_coeffs(self, n_blk):
-        """_terms_from_sums(...)["loss"] as a coefficient vector over the sums buffer (16 floats per slot)"""
-        lay = self.layout
-        c = np.zeros((len(_SLOTS), 16))
-        c[0, :6], c[0, 6:12] = lay["f_uv"] / n_blk, lay["f_s"] / n_blk
-        for k, name in enumerate(_SLOTS[1:], start=1):
-            if name in self._sides and name in lay:
-                c[k, list(self._sides[name][5])] = lay[name] / self._sides[name][6]
-        return c.reshape(-1).tolist()
-
     def train_bfgs(self, batch_num, options: Optional[dict] = None, backend: str = "scipy"):
         """L-BFGS stage on the device kernels, as SEMI:330-344.  ``backend="scipy"`` (default): scipy's L-BFGS-B on the host over a float64
-        copy of the flat vector; ``"torch"``: torch.optim.LBFGS on the device (elastic_wave.lbfgs_on_device); ``"hip"``: the library's own
-        L-BFGS, no host round trip per evaluation (elastic_wave.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError."""
+        copy of the flat vector; ``"torch"``: torch.optim.LBFGS on the device (optim.lbfgs_on_device); ``"hip"``: the library's own
+        L-BFGS, no host round trip per evaluation (optim.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError."""
         check_backend(backend)
-        P, L = self.n_params, len(_SLOTS)
+        L = len(_SLOTS)
         opts = dict(maxiter=1000, maxfun=1000, maxcor=50, maxls=50, ftol=0.001 * float(np.finfo(float).eps))       # SEMI:130-137
         if options:
             opts.update(options)
@@ -360,26 +225,8 @@ class NavierCauchy3D(NetApi):
                 self._loss_and_grad(lo, hi)
                 return self._buf
 
-            def fun(theta64):
-                self.theta.copy_(torch.from_numpy(theta64.astype(np.float32)).to(self.device))
-                host = evaluate_with_finite_gradient(self.engine, evaluate, P, self._shift_state, check=self._check_collective)
-                tm = self._terms_from_sums(host[P:].reshape(L, 16), hi - lo)
-                self.callback(tm["loss"])
-                return tm["loss"], host[:P].astype(np.float64)
-
-            if backend == "torch":
-                def loss_and_grad():
-                    host = evaluate_with_finite_gradient(self.engine, evaluate, 0, self._shift_state, device_check=P, check=self._check_collective)
-                    return self._terms_from_sums(host.reshape(L, 16), hi - lo)["loss"], self._buf[:P]
-                result = lbfgs_on_device(self.theta, loss_and_grad, opts, self.callback)
-                continue
-            if backend == "hip":
-                result = lbfgs_hip(self.engine, self.theta, evaluate, P, self._loss_coeffs(hi - lo), opts, self.callback,
-                                   check=self._check_collective, shift_state=self._shift_state)
-                continue
-            import scipy.optimize
-            result = scipy.optimize.minimize(fun, self.theta.detach().cpu().numpy().astype(np.float64), jac=True, method='L-BFGS-B', options=opts)
-            self.theta.copy_(torch.from_numpy(result.x.astype(np.float32)).to(self.device))
+            result = self._lbfgs_stage(backend, self.engine, self.theta, evaluate,
+                                       lambda sums: self._terms_from_sums(sums.reshape(L, 16), hi - lo)["loss"], self._loss_coeffs(hi - lo), opts)
         return result
 
     # ---- inference / diagnostics ---------------------------------------------------------------------------------------

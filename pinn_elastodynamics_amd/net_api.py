@@ -14,6 +14,9 @@ import pickle
 from typing import Sequence
 
 import numpy as np
+import torch
+
+from .optim import pack_params, truncated_normal  # noqa: F401
 
 _NUMPY_GLOBALS = {
     ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
@@ -59,16 +62,6 @@ def write_checkpoint(fileDir, weights, biases, layers):
             pickle.dump([list(weights), list(biases)], f)
 
 
-def truncated_normal(rng: np.random.Generator, shape, stddev: float) -> np.ndarray:
-    """tf.truncated_normal (INF:156): normal draws, redrawn while |z| > 2 standard deviations"""
-    W = rng.standard_normal(shape)
-    bad = np.abs(W) > 2.0
-    while bad.any():
-        W[bad] = rng.standard_normal(int(bad.sum()))
-        bad = np.abs(W) > 2.0
-    return (W * stddev).astype(np.float32)
-
-
 class NetApi:
     """Mixin: expects ``self._init_rng`` (numpy Generator), ``self.uv_layers``, ``self.engine`` and ``self._net_fields(engine, theta, X)``
     (the value-stream outputs [n_out, N] of a net on points X [N, d_in])."""
@@ -101,8 +94,6 @@ class NetApi:
     def neural_net(self, X, weights=None, biases=None):
         """INF:188-199 on X [N, d_in] -> Y [N, n_out], with the weights handed in (lists as initialize_NN / load_NN return them) or, when
         none are given, the model's current ones.  The input normalisation is the model's (INF:191 on, SEMI:198 / PLATE:312 off)."""
-        import torch
-        from .elastic_wave import pack_params
         X = np.asarray(X)
         if weights is None:
             eng, theta = self.engine, self._current_theta()

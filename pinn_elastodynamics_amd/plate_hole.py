@@ -16,8 +16,8 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .elastic_wave import _col, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device, pack_params, relax_adjoint_shift, unpack_params, xavier_init  # noqa: F401
-from .net_api import NetApi, read_checkpoint, write_checkpoint
+from .model_base import ModelBase
+from .optim import all_reduce_sum, check_backend, device_array, lbfgs_hip, lbfgs_on_device, pack_params
 from .refine import Candidates, empty_result, schedule, score_weights, select_pairs, update_host_columns
 from .validate import PredictMixin, schedule as validate_schedule
 
@@ -29,7 +29,7 @@ BFGS_OPTIONS = {   # PLATE:220-247
 }
 
 
-class PINN(NetApi, PredictMixin):
+class PINN(ModelBase, PredictMixin):
     def __init__(self, Collo, HOLE, IC, LF, RT, UP, LW, DIST, uv_layers, dist_layers, part_layers, lb, ub,
                  partDir='', distDir='', uvDir='', *, precision="f16x3", engines=None, seed=1111, process_group=None, verbose=True,
                  always_reduce=False, collective="rccl", p2p_timeout_s=None):
@@ -42,25 +42,14 @@ class PINN(NetApi, PredictMixin):
         self.dist_layers = [int(v) for v in dist_layers]
         self.part_layers = [int(v) for v in part_layers]
         self.verbose = verbose
-        self.pg = process_group
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            self.rank, self.world = torch.distributed.get_rank(self.pg), torch.distributed.get_world_size(self.pg)
-        else:
-            self.rank, self.world = 0, 1
-        # (always_reduce: the collective branch also at one rank -- see elastic_wave.DeepHPM)
-        self._reduce = self.world > 1 or (bool(always_reduce) and torch.distributed.is_available() and torch.distributed.is_initialized())
-
+        self._init_topology(process_group, always_reduce)
         if engines is None:
-            from .hip_engine import HipEngine
-            n_max = max(int(np.asarray(Collo).shape[0]) // self.world + 1, 1 << 14)
-            engines = {k: HipEngine(l, precision=precision, max_points=n_max)
+            engines = {k: self._default_engine(l, precision, np.asarray(Collo).shape[0])
                        for k, l in (("uv", self.uv_layers), ("dist", self.dist_layers), ("part", self.part_layers))}
         self.eng = engines
-        self.device = engines["uv"].device
-
-        self.engine = engines["uv"]            # (net_api.NetApi's default engine; nets of other sizes find theirs in _engine_for)
-        if hasattr(self.engine, "warn_if_slow_path"):
-            self.engine.warn_if_slow_path("plate")      # (the frozen 4 x 20 nets are evaluated once: their path does not matter)
+        # (net_api.NetApi's default engine; nets of other sizes find theirs in _engine_for.  The frozen 4 x 20 nets are evaluated once: their
+        # path does not matter)
+        self._set_engine(engines["uv"], "plate")
         self._init_rng = np.random.default_rng(seed)
         self.theta, self.adam_m, self.adam_v = {}, {}, {}
         for key, layers, d in (("dist", self.dist_layers, distDir), ("part", self.part_layers, partDir), ("uv", self.uv_layers, uvDir)):
@@ -72,12 +61,12 @@ class PINN(NetApi, PredictMixin):
         self.adam_t = 0
 
         def dev(a):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+            return device_array(a, self.device)
 
         def xyt(A, shard=True):
             A = np.asarray(A, dtype=np.float64)
             s, e = self._shard(0, A.shape[0]) if shard else (0, A.shape[0])
-            return A[s:e], tuple(dev(_col(A[s:e, k])) for k in range(3))
+            return A[s:e], tuple(self._device_columns(A[s:e, k] for k in range(3)))
 
         Collo = np.asarray(Collo, dtype=np.float64)
         self.x_c, self.y_c, self.t_c = Collo[:, 0:1], Collo[:, 1:2], Collo[:, 2:3]
@@ -114,32 +103,8 @@ class PINN(NetApi, PredictMixin):
                 tgt = dev(tg)
             self._part_sets.append((xyt(A, False)[1], tgt, w, A.shape[0]))
         self._buf = torch.zeros(self.theta["uv"].numel() + 16, dtype=torch.float32, device=self.device)
-        # collective: "rccl" (torch.distributed.all_reduce) or "p2p" (the library's one-shot all-reduce over IPC-mapped peer buffers; elastic_wave.DeepHPM)
-        if collective not in ("rccl", "p2p"):
-            raise ValueError("collective must be 'rccl' or 'p2p'")
-        self._p2p = None
-        if collective == "p2p" and self._reduce:
-            if not hasattr(self.eng["uv"], "lib"):
-                raise ValueError("collective='p2p' needs the HIP engine")
-            from .p2p import P2PAllReduce
-            self._p2p = P2PAllReduce(self.eng["uv"].lib, self._buf.numel(), self.pg, timeout_s=p2p_timeout_s)
+        self._init_collective(collective, p2p_timeout_s)
         self.refresh_frozen()
-
-    def _check_collective(self):
-        """collective='p2p': raise if a one-shot all-reduce has failed on this rank (elastic_wave.DeepHPM._check_collective)"""
-        if getattr(self, "_p2p", None) is not None:
-            self._p2p.check()
-
-    def close(self):
-        """Release the P2P communicator (collective: every rank calls it).  Nothing to do for collective='rccl'."""
-        p2p, self._p2p = getattr(self, "_p2p", None), None
-        if p2p is not None:
-            p2p.close()
-
-    # ------------------------------------------------------------------------------------------------------------------
-    def _shard(self, lo, hi):
-        n = hi - lo
-        return lo + n * self.rank // self.world, lo + n * (self.rank + 1) // self.world
 
     def refresh_frozen(self):
         """(Re)compute the streams of the frozen distance / particular nets on the collocation and hole points."""
@@ -160,16 +125,7 @@ class PINN(NetApi, PredictMixin):
         if key is None:
             return
         layers = {"uv": self.uv_layers, "dist": self.dist_layers, "part": self.part_layers}[key]
-        W, b = unpack_params(self.theta[key].detach().cpu().numpy(), layers)
-        write_checkpoint(fileDir, W, b, layers)          # .npz: plain arrays (documented default); otherwise the reference's pickle
-        if self.verbose:
-            print("Save " + TYPE + " NN parameters successfully...")
-
-    def load_NN(self, fileDir, layers):
-        uv_weights, uv_biases = read_checkpoint(fileDir)       # .npz, or the reference's pickle through the arrays-only unpickler
-        assert len(layers) == (len(uv_weights) + 1)                                           # PLATE:299
-        return ([np.asarray(w, dtype=np.float32) for w in uv_weights],
-                [np.asarray(b, dtype=np.float32).reshape(1, -1) for b in uv_biases])
+        self._save_net(fileDir, self.theta[key], layers)
 
     # ---- neural_net(X, weights, biases) (PLATE:308-320; PLATE:322-356 runs all three nets through it): net_api.NetApi ------------
     def _current_theta(self):
@@ -183,17 +139,13 @@ class PINN(NetApi, PredictMixin):
         return super()._engine_for(layers)
 
     def _net_fields(self, eng, theta, X):
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(X[:, k]), dtype=np.float32)).to(eng.device) for k in range(3)]
+        xs = self._device_columns((X[:, k] for k in range(3)), eng.device)
         return eng.net_streams(theta, xs[0], xs[1], xs[2], self.lb, self.ub, False)[0]
 
     # ---- graph pieces on column arrays --------------------------------------------------------------------------------
     def _streams(self, key, x, y, t):
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, t)]
+        xs = self._device_columns((x, y, t))
         return self.eng[key].net_streams(self.theta[key], xs[0], xs[1], xs[2], self.lb, self.ub, False)
-
-    @staticmethod
-    def _cols(T):
-        return tuple(T[i].detach().cpu().numpy().reshape(-1, 1) for i in range(T.shape[0]))
 
     def _composite(self, x, y, t):
         N, D, P = (self._streams(k, x, y, t) for k in ("uv", "dist", "part"))
@@ -264,7 +216,7 @@ class PINN(NetApi, PredictMixin):
         """sum_i weights[i] * f_i^2 of net_f_sig's five residuals (PLATE:404-439) per point, numpy [N,1]: the D and P streams at the points,
         then one score call on the uv net that forms the composite and the residuals in the kernel.  Default ``weights``: [10] * 5."""
         w = self._score_weights(weights)
-        xs = [torch.from_numpy(np.ascontiguousarray(_col(a), dtype=np.float32)).to(self.device) for a in (x, y, t)]
+        xs = self._device_columns((x, y, t))
         if xs[0].numel() == 0:
             return np.zeros((0, 1), dtype=np.float32)
         return self._score_device(xs, self._frozen_at(xs), w).detach().cpu().numpy().reshape(-1, 1)
@@ -375,10 +327,8 @@ class PINN(NetApi, PredictMixin):
             self._loss_and_grad()
             return self._buf
 
-        if iter > 0 and getattr(self.eng["uv"], "needs_finite_probe", False) and not self._shift_state.get("probed"):
-            # once per model: settle the adjoint shift (E = 20 makes the plate's early residuals large)
-            evaluate_with_finite_gradient(self.eng["uv"], probe, P, self._shift_state, check=self._check_collective)
-            self._shift_state["probed"] = True
+        if iter > 0:
+            self._settle_adjoint_shift(self.eng["uv"], probe, P)      # (E = 20 makes the plate's early residuals large)
         for it in range(iter):
             self.adam_t += 1
             updated = self._loss_and_grad(adam=(learning_rate, self.adam_t))
@@ -406,37 +356,18 @@ class PINN(NetApi, PredictMixin):
         return res
 
     def train_bfgs(self, options: Optional[dict] = None, backend: str = "scipy"):          # PLATE:508-526
-        """backend="torch": the optimizer runs on the device too (elastic_wave.lbfgs_on_device); backend="hip": the library's own L-BFGS, no host
-        round trip per evaluation (elastic_wave.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError."""
+        """backend="torch": the optimizer runs on the device too (optim.lbfgs_on_device); backend="hip": the library's own L-BFGS, no host
+        round trip per evaluation (optim.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError."""
         check_backend(backend)
-        P = self.theta["uv"].numel()
 
         def evaluate():
             self._loss_and_grad()
             return self._buf
 
-        def fun(th):
-            self.theta["uv"].copy_(torch.from_numpy(th.astype(np.float32)).to(self.device))
-            host = evaluate_with_finite_gradient(self.eng["uv"], evaluate, P, self._shift_state, check=self._check_collective)
-            loss = self._terms(host[P:])["loss"]
-            relax_adjoint_shift(self.eng["uv"], loss, self._shift_state)
-            self.callback(loss)
-            return loss, host[:P].astype(np.float64)
-
-        opts = dict(BFGS_OPTIONS["uv"], **(options or {}))
-        if backend == "torch":
-            def loss_and_grad():
-                host = evaluate_with_finite_gradient(self.eng["uv"], evaluate, 0, self._shift_state, device_check=P, check=self._check_collective)
-                loss = self._terms(host)["loss"]
-                relax_adjoint_shift(self.eng["uv"], loss, self._shift_state)
-                return loss, self._buf[:P]
-            return lbfgs_on_device(self.theta["uv"], loss_and_grad, opts, self.callback)
-        if backend == "hip":
-            c = np.zeros(16)                             # _terms(...)["loss"] as coefficients of the 16 sums
-            c[0:5], c[8:10] = 10.0 / self.n_collo, 10.0 / self.n_hole
-            return lbfgs_hip(self.eng["uv"], self.theta["uv"], evaluate, P, c.tolist(), opts, self.callback, check=self._check_collective,
-                             shift_state=self._shift_state)
-        return self._bfgs("uv", fun, opts)
+        c = np.zeros(16)                                 # _terms(...)["loss"] as coefficients of the 16 sums
+        c[0:5], c[8:10] = 10.0 / self.n_collo, 10.0 / self.n_hole
+        return self._lbfgs_stage(backend, self.eng["uv"], self.theta["uv"], evaluate, lambda sums: self._terms(sums)["loss"], c.tolist(),
+                                 dict(BFGS_OPTIONS["uv"], **(options or {})))
 
     def _pretrain_loss_grad(self, key, sets):
         """sum over sets of mean-square terms (PLATE:194-215); returns (loss, grad) on the host."""

@@ -13,6 +13,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .optim import device_column
+
 
 def pair_replacements(cand_idx, cand_score, row_idx, row_score):
     """The pairing rule of refine_collocation on the K selected candidates and the K selected rows (torch tensors on any device; the index
@@ -44,7 +46,7 @@ def candidate_array(candidates, ncols, names):
 
 
 def device_columns(C, device):
-    return tuple(torch.from_numpy(np.ascontiguousarray(C[:, k], dtype=np.float32)).to(device) for k in range(C.shape[1]))
+    return tuple(device_column(C[:, k], device) for k in range(C.shape[1]))
 
 
 def empty_result():

@@ -8,12 +8,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-
-def device_column(a, device):
-    """a numpy column ([N,1] or [N]) or a device tensor -> contiguous fp32 device tensor [N]"""
-    if isinstance(a, torch.Tensor):
-        return a.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.float32)).to(device)
+from .optim import device_column
 
 
 def tile_frames(space_cols, times, device):

@@ -41,17 +41,26 @@ class LbfgsOracleEngine(LbfgsMixin, OracleEngine):
 
 
 class OverflowingEngine(LbfgsOracleEngine):
-    """The 16-bit reverse pass overflowing: from the `nan_from`-th wave evaluation on, the gradient comes back NaN (the sums stay right) until
-    adjoint_shift has been raised"""
+    """The 16-bit reverse pass overflowing: from the `nan_from`-th collocation evaluation (wave or 3-D) on, the gradient comes back NaN (the sums
+    stay right) until adjoint_shift has been raised.  `nan_until`: only up to that evaluation -- the residuals are large at the start of a stage
+    and fall, so a shift that was lowered again is not forced back up"""
 
-    def __init__(self, layers, nan_from):
+    def __init__(self, layers, nan_from, nan_until=None):
         super().__init__(layers)
-        self.nan_from, self.wave_calls, self.poisoned = nan_from, 0, 0
+        self.nan_from, self.nan_until, self.wave_calls, self.poisoned = nan_from, nan_until, 0, 0
+
+    def _poison(self, grad_out):
+        self.wave_calls += 1
+        if self.adjoint_shift < 4 and self.wave_calls > self.nan_from and (self.nan_until is None or self.wave_calls <= self.nan_until):
+            grad_out.fill_(float("nan"))
+            self.poisoned += 1
 
     def wave_loss_grad(self, *a, **kw):
         out = super().wave_loss_grad(*a, **kw)
-        self.wave_calls += 1
-        if self.adjoint_shift < 4 and self.wave_calls > self.nan_from:
-            kw["grad_out"].fill_(float("nan"))
-            self.poisoned += 1
+        self._poison(kw["grad_out"])
+        return out
+
+    def nc3d_loss_grad(self, *a, **kw):
+        out = super().nc3d_loss_grad(*a, **kw)
+        self._poison(kw["grad_out"])
         return out

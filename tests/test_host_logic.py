@@ -111,6 +111,19 @@ def test_confined_signature():
     assert m.case == "confined" and not m.normalize and "FIX" in m._sides
 
 
+def test_confined_getloss_checks_the_collective():
+    """getloss synchronises with the host: a failed one-shot all-reduce raises there, in the confined class as in DeepHPM"""
+    class FailedCollective:
+        def check(self):
+            raise RuntimeError("one-shot all-reduce failed")
+    Collo, SRC, IC, UP = small_sets()
+    for m in (DeepHPM(Collo, SRC, IC, UP, LAYERS, LB, UB, engine=OracleEngine(LAYERS), verbose=False),
+              DeepHPMConfined(Collo, SRC, IC, UP, None, LAYERS, [3, 30, 5], [3, 20, 5], LB, UB, engine=OracleEngine(LAYERS), verbose=False)):
+        m._p2p = FailedCollective()
+        with pytest.raises(RuntimeError, match="one-shot all-reduce failed"):
+            m.getloss()
+
+
 def test_data_parallel_two_ranks_matches_single(tmp_path):
     """world_size-2 gloo run: sharded sets + one all-reduce give the single-process weights."""
     script = os.path.join(ROOT, "tests", "_dp_worker.py")

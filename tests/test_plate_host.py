@@ -164,6 +164,21 @@ def test_plate_three_stage_schedule_and_predict(tmp_path):
         np.testing.assert_array_equal(m.theta[k].numpy(), m2.theta[k].numpy())
 
 
+def test_plate_load_NN_refuses_a_transposed_matrix(tmp_path):
+    """a checkpoint with the right number of layers whose first matrix is stored [out, in]: load_NN asserts the shapes, as the wave classes do"""
+    from pinn_elastodynamics_amd.net_api import write_checkpoint
+    m, _ = make_model(3)
+    W, b = po.unpack_params(m.theta["uv"].numpy(), LN)
+    for name in ("uv.pickle", "uv.npz"):
+        p = str(tmp_path / name)
+        write_checkpoint(p, W, b, LN)
+        W2, _ = m.load_NN(p, LN)
+        np.testing.assert_array_equal(W2[0], W[0])
+        write_checkpoint(p, [W[0].T.copy()] + W[1:], b, LN)
+        with pytest.raises(AssertionError):
+            m.load_NN(p, LN)
+
+
 def test_plate_data_parallel_two_ranks(tmp_path):
     """world_size-2 gloo run of the plate model: collocation and hole sets sharded, one all-reduce per evaluation, Adam and
     the host L-BFGS run redundantly on every rank from the identical reduced loss / gradient."""
