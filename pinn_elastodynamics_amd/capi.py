@@ -108,9 +108,89 @@ class PinnLibError(RuntimeError):
     pass
 
 
+# ---- prototypes: symbol -> (restype, argtypes) of EVERY function include/pinn_hip.h declares, a row per declaration in the header's order and
+# spelling.  Module-level data: tests/test_capi_header.py holds it to the header without loading a library; PinnLib.__init__ applies it.
+_vp, _i32, _i64, _f64, _sz, _u32, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_uint32, C.c_uint64
+_pi32, _pf64, _pf32, _psz = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_size_t)
+_NET = [_vp, _pi32, _i32]                          # params_flat, layers, n_layers
+_BOX = [_pf64, _pf64, _i32]                        # lb, ub, normalize
+_PTS3 = [_vp, _vp, _vp, _i64] + _BOX               # x, y, t, n + box
+_PTS4 = [_vp, _vp, _vp, _vp, _i64] + _BOX          # x, y, z, t, n + box
+_MAT = [_f64, _f64, _f64]                          # E, mu, rho
+_WAVE = _MAT + [_i32, _pf32]                       # + plane_strain, term_weights[7]
+_OUT = [_vp, _vp, _i32]                            # loss_terms_out, grad_flat_out, accumulate
+_TAIL = [_i32, _vp, _sz, _vp]                      # precision_mode, workspace, ws_bytes, stream
+_ADAM = C.POINTER(AdamState)
+PROTOTYPES = {
+    "pinn_supported_width": (_i32, [_i32]),
+    "pinn_fused_weight_limit": (C.c_float, []),
+    "pinn_path_for": (_i32, [_pi32, _i32, _i32, _i32, _sz]),
+    "pinn_debug_path_counts": (None, [_vp, _i32]),
+    "pinn_workspace_bytes": (_sz, [_pi32, _i32, _i64, _i32]),
+    "pinn_min_workspace_bytes": (_sz, [_pi32, _i32, _i32]),
+    "pinn_wave2d_loss_grad": (_i32, _NET + _PTS3 + _WAVE + _OUT + _TAIL),
+    "pinn_wave2d_loss_grad_profile": (_i32, _NET + _PTS3 + _WAVE + _OUT + _TAIL + [_pf32]),
+    "pinn_data_loss_grad": (_i32, _NET + _PTS3 + [_vp, _pf32] + _OUT + _TAIL),
+    "pinn_wave2d_fields": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
+    "pinn_wave2d_residual_score": (_i32, _NET + _PTS3 + _WAVE + [_vp] + _TAIL),
+    "pinn_wave2d_predict": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
+    "pinn_field_error_workspace_bytes": (_sz, [_i64, _i32]),
+    "pinn_field_error_sums": (_i32, [_vp, _i64, _pi32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "pinn_select_workspace_bytes": (_sz, [_i64]),
+    "pinn_select_k": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "pinn_sample_box": (_i32, [_u64, _u32, _u64, _i64, _i32, _pf64, _pf64, _vp, _vp, _vp, _vp, _vp]),
+    "pinn_refine_keys_workspace_bytes": (_sz, [_i64]),
+    "pinn_refine_keys": (_i32, [_vp, _i64, _vp, _vp, _vp, C.POINTER(Ball), _i32, _i32, _f64, _f64, _u64, _u32, _u64, _vp, _vp, _sz, _vp]),
+    "pinn_net_streams": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
+    "pinn_plate2d_loss_grad": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32] + _OUT + _TAIL),
+    "pinn_plate2d_residual_score": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32, _vp] + _TAIL),
+    "pinn_plate2d_predict": (_i32, _NET + _PTS3 + [_vp, _vp] + _TAIL),
+    "pinn_plate2d_traction_loss_grad": (_i32, _NET + _PTS3 + [_vp, _pf32] + _OUT + _TAIL),
+    "pinn_stream_loss_grad": (_i32, _NET + _PTS3 + [_vp, _pf32] + _OUT + _TAIL),
+    "pinn_stream_loss_grad_multi": (_i32, _NET + [C.POINTER(StreamSet), _i32] + _BOX + [_vp, _i32] + _TAIL),
+    "pinn_probe_ranges": (_i32, [_vp, _vp, _i64, _vp, _sz, _vp, _pi32, _pf32]),
+    # (no `accumulate` argument, a pinn_range_state at the end)
+    "pinn_wave2d_loss_grad_checked": (_i32, _NET + _PTS3 + _WAVE + [_vp, _vp] + _TAIL + [C.POINTER(RangeState)]),
+    "pinn_data_loss_grad_multi": (_i32, _NET + [C.POINTER(PointSet), _i32] + _BOX + [_vp, _i32] + _TAIL),
+    "pinn_wave2d_step": (_i32, _NET + _PTS3 + _WAVE + [_vp, C.POINTER(PointSet), _i32, _vp, _i32, _ADAM] + _TAIL),
+    "pinn_plate2d_step": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32, _vp, _vp, _vp, _vp, _i64, _vp, _pf32, _vp, _vp, _i32, _ADAM] + _TAIL),
+    "pinn_nc3d_loss_grad": (_i32, _NET + _PTS4 + _MAT + [_pf32] + _OUT + _TAIL),
+    "pinn_nc3d_data_loss_grad": (_i32, _NET + _PTS4 + [_vp, _pf32] + _OUT + _TAIL),
+    "pinn_nc3d_fields": (_i32, _NET + _PTS4 + [_vp] + _TAIL),
+    "pinn_nc3d_residual_score": (_i32, _NET + _PTS4 + _MAT + [_pf32, _vp] + _TAIL),
+    "pinn_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _vp]),
+    "pinn_lbfgs_state_bytes": (_sz, [_i64, _i32]),
+    "pinn_lbfgs_init": (_i32, [_vp, _sz, _i64, C.POINTER(LbfgsOptions), _pf32, _i32, _f64, _vp]),
+    "pinn_lbfgs_advance": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "pinn_lbfgs_status": (_i32, [_vp, C.POINTER(LbfgsRecord), _vp]),
+    "pinn_lbfgs_read_losses": (_i32, [_vp, _i64, _i64, _pf64, _vp]),
+    "pinn_lbfgs_debug_read": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _pi32, _vp]),
+    "pinn_p2p_create": (_i32, [_i32, _i32, _i64, C.POINTER(_vp), _vp]),
+    "pinn_p2p_connect": (_i32, [_vp, _vp]),
+    "pinn_p2p_set_timeout_ms": (_i32, [_vp, _f64]),
+    "pinn_p2p_allreduce": (_i32, [_vp, _vp, _i64, _vp, _ADAM, _i64, _vp]),
+    "pinn_p2p_status": (_i32, [_vp, _pi32]),
+    "pinn_p2p_peek_status": (_i32, [_vp]),
+    "pinn_p2p_destroy": (_i32, [_vp]),
+    "pinn_p2p_debug_force_coarse": (_i32, [_i32]),
+    "pinn_debug_set_fused": (_i32, [_i32]),
+    "pinn_debug_set_xcd_bonus": (_i32, [_i32]),
+    "pinn_debug_set_fused_grid_cap": (_i32, [_i32]),
+    "pinn_debug_cache_policy": (_i32, [_pi32, _i32, _i32, _psz, _psz]),
+    "pinn_debug_set_stamp_buffer": (None, [_vp]),
+    "pinn_debug_wall_clock_khz": (_i32, []),
+    "pinn_debug_set_profile_buffer": (None, [_vp]),
+    "pinn_debug_profile_ring_arm": (_i32, [_i32]),
+    "pinn_debug_profile_ring_stride": (None, [_i32]),
+    "pinn_debug_profile_ring_read": (_i32, [_vp, _vp, _i32]),
+    "pinn_error_string": (C.c_char_p, [_i32]),
+    "pinn_abi_version": (_i32, []),
+}
+
 # The profiling hook of the library is process-wide and keeps a raw host pointer: the buffer it writes to is owned HERE, at module
 # level, for as long as the hook is on -- never by a PinnLib instance that may be collected while another engine still launches.
 _PROFILE_BUFFER = None
+_F8 = C.c_float * 8
 
 
 class PinnLib:
@@ -123,120 +203,12 @@ class PinnLib:
                 "(or `make -C pinn_elastodynamics_amd/csrc hip`). There is no CPU fallback.")
         self.path = path
         self.lib = C.CDLL(path)
-        L = self.lib
-        vp, i32, i64, f64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t
-        pi32, pf64, pf32 = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
-        L.pinn_abi_version.restype = i32
-        L.pinn_supported_width.argtypes = [i32]
-        L.pinn_supported_width.restype = i32
-        L.pinn_error_string.argtypes = [i32]
-        L.pinn_error_string.restype = C.c_char_p
-        L.pinn_workspace_bytes.argtypes = [pi32, i32, i64, i32]
-        L.pinn_workspace_bytes.restype = sz
-        L.pinn_min_workspace_bytes.argtypes = [pi32, i32, i32]
-        L.pinn_min_workspace_bytes.restype = sz
-        L.pinn_wave2d_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, i32, pf32,
-                                            vp, vp, i32, i32, vp, sz, vp]
-        L.pinn_wave2d_loss_grad.restype = i32
-        L.pinn_wave2d_loss_grad_profile.argtypes = L.pinn_wave2d_loss_grad.argtypes + [pf32]
-        L.pinn_wave2d_loss_grad_profile.restype = i32
-        # (round 6) the finite-gradient ladder as library calls: no `accumulate` argument, a pinn_range_state at the end
-        L.pinn_wave2d_loss_grad_checked.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, i32, pf32,
-                                                    vp, vp, i32, vp, sz, vp, C.POINTER(RangeState)]
-        L.pinn_wave2d_loss_grad_checked.restype = i32
-        L.pinn_probe_ranges.argtypes = [vp, vp, i64, vp, sz, vp, C.POINTER(i32), pf32]
-        L.pinn_probe_ranges.restype = i32
-        L.pinn_data_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
-        L.pinn_data_loss_grad.restype = i32
-        L.pinn_data_loss_grad_multi.argtypes = [vp, pi32, i32, C.POINTER(PointSet), i32, pf64, pf64, i32, vp, i32, i32, vp, sz, vp]
-        L.pinn_data_loss_grad_multi.restype = i32
-        L.pinn_wave2d_step.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, i32, pf32, vp, C.POINTER(PointSet), i32, vp, i32,
-                                       C.POINTER(AdamState), i32, vp, sz, vp]
-        L.pinn_wave2d_step.restype = i32
-        L.pinn_plate2d_step.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, vp, vp, vp, i64, vp, pf32, vp, vp, i32,
-                                        C.POINTER(AdamState), i32, vp, sz, vp]
-        L.pinn_plate2d_step.restype = i32
-        L.pinn_wave2d_fields.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, i32, vp, sz, vp]
-        L.pinn_wave2d_fields.restype = i32
-        L.pinn_net_streams.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, i32, vp, sz, vp]
-        L.pinn_net_streams.restype = i32
-        L.pinn_wave2d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, i32, pf32, vp, i32, vp, sz, vp]
-        L.pinn_wave2d_residual_score.restype = i32
-        L.pinn_wave2d_predict.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, i32, vp, sz, vp]
-        L.pinn_wave2d_predict.restype = i32
-        L.pinn_plate2d_predict.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, vp, i32, vp, sz, vp]
-        L.pinn_plate2d_predict.restype = i32
-        L.pinn_field_error_workspace_bytes.argtypes = [i64, i32]
-        L.pinn_field_error_workspace_bytes.restype = sz
-        L.pinn_field_error_sums.argtypes = [vp, i64, pi32, i32, vp, i64, vp, vp, sz, vp]
-        L.pinn_field_error_sums.restype = i32
-        L.pinn_select_workspace_bytes.argtypes = [i64]
-        L.pinn_select_workspace_bytes.restype = sz
-        L.pinn_select_k.argtypes = [vp, i64, i64, i32, vp, vp, sz, vp]
-        L.pinn_select_k.restype = i32
-        u64, u32 = C.c_uint64, C.c_uint32
-        L.pinn_sample_box.argtypes = [u64, u32, u64, i64, i32, pf64, pf64, vp, vp, vp, vp, vp]
-        L.pinn_sample_box.restype = i32
-        L.pinn_refine_keys_workspace_bytes.argtypes = [i64]
-        L.pinn_refine_keys_workspace_bytes.restype = sz
-        L.pinn_refine_keys.argtypes = [vp, i64, vp, vp, vp, C.POINTER(Ball), i32, i32, f64, f64, u64, u32, u64, vp, vp, sz, vp]
-        L.pinn_refine_keys.restype = i32
-        L.pinn_plate2d_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, vp, i32, i32, vp, sz, vp]
-        L.pinn_plate2d_loss_grad.restype = i32
-        L.pinn_plate2d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, f64, f64, f64, pf32, vp, i32, vp, sz, vp]
-        L.pinn_plate2d_residual_score.restype = i32
-        L.pinn_nc3d_residual_score.argtypes = [vp, pi32, i32, vp, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, pf32, vp, i32, vp, sz, vp]
-        L.pinn_nc3d_residual_score.restype = i32
-        L.pinn_plate2d_traction_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
-        L.pinn_plate2d_traction_loss_grad.restype = i32
-        L.pinn_stream_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
-        L.pinn_stream_loss_grad.restype = i32
-        L.pinn_stream_loss_grad_multi.argtypes = [vp, pi32, i32, C.POINTER(StreamSet), i32, pf64, pf64, i32, vp, i32, i32, vp, sz, vp]
-        L.pinn_stream_loss_grad_multi.restype = i32
-        L.pinn_nc3d_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, vp, i64, pf64, pf64, i32, f64, f64, f64, pf32, vp, vp, i32, i32, vp, sz, vp]
-        L.pinn_nc3d_loss_grad.restype = i32
-        L.pinn_nc3d_data_loss_grad.argtypes = [vp, pi32, i32, vp, vp, vp, vp, i64, pf64, pf64, i32, vp, pf32, vp, vp, i32, i32, vp, sz, vp]
-        L.pinn_nc3d_data_loss_grad.restype = i32
-        L.pinn_nc3d_fields.argtypes = [vp, pi32, i32, vp, vp, vp, vp, i64, pf64, pf64, i32, vp, i32, vp, sz, vp]
-        L.pinn_nc3d_fields.restype = i32
-        L.pinn_adam_step.argtypes = [vp, vp, vp, vp, i64, f64, f64, f64, f64, i64, vp]
-        L.pinn_adam_step.restype = i32
-        if hasattr(L, "pinn_lbfgs_init"):              # (one-variant experiment builds of older trees do not have the device L-BFGS)
-            L.pinn_lbfgs_state_bytes.argtypes = [i64, i32]
-            L.pinn_lbfgs_state_bytes.restype = sz
-            L.pinn_lbfgs_init.argtypes = [vp, sz, i64, C.POINTER(LbfgsOptions), pf32, i32, f64, vp]
-            L.pinn_lbfgs_init.restype = i32
-            L.pinn_lbfgs_advance.argtypes = [vp, vp, vp, vp, vp]
-            L.pinn_lbfgs_advance.restype = i32
-            L.pinn_lbfgs_status.argtypes = [vp, C.POINTER(LbfgsRecord), vp]
-            L.pinn_lbfgs_status.restype = i32
-            L.pinn_lbfgs_read_losses.argtypes = [vp, i64, i64, pf64, vp]
-            L.pinn_lbfgs_read_losses.restype = i32
-            L.pinn_lbfgs_debug_read.argtypes = [vp, i64, i32, vp, vp, vp, i32, pi32, vp]
-            L.pinn_lbfgs_debug_read.restype = i32
-        L.pinn_debug_set_profile_buffer.argtypes = [vp]
-        L.pinn_debug_set_profile_buffer.restype = None
-        if hasattr(L, "pinn_debug_set_xcd_bonus"):      # (tuning hook; experiment builds of older trees do not have it)
-            L.pinn_debug_set_xcd_bonus.argtypes = [i32]
-            L.pinn_debug_set_xcd_bonus.restype = i32
-        L.pinn_debug_set_fused.argtypes = [i32]
-        L.pinn_debug_set_fused.restype = i32
-        L.pinn_fused_weight_limit.argtypes = []
-        L.pinn_fused_weight_limit.restype = C.c_float
-        L.pinn_path_for.argtypes = [pi32, i32, i32, i32, sz]
-        L.pinn_path_for.restype = i32
-        L.pinn_debug_path_counts.argtypes = [vp, i32]
-        L.pinn_debug_path_counts.restype = None
-        L.pinn_debug_profile_ring_stride.argtypes = [i32]
-        L.pinn_debug_profile_ring_stride.restype = None
-        L.pinn_debug_wall_clock_khz.argtypes = []
-        L.pinn_debug_wall_clock_khz.restype = i32
-        L.pinn_debug_set_stamp_buffer.argtypes = [vp]
-        L.pinn_debug_set_stamp_buffer.restype = None
-        L.pinn_debug_profile_ring_arm.argtypes = [i32]
-        L.pinn_debug_profile_ring_arm.restype = i32
-        L.pinn_debug_profile_ring_read.argtypes = [vp, vp, i32]
-        L.pinn_debug_profile_ring_read.restype = i32
+        # every entry of the table the library exports (one-variant experiment builds of older trees lack the newest ones; the product library is held
+        # to the full set by tests/test_capi_symbols.py)
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(self.lib, name, None)
+            if fn is not None:
+                fn.restype, fn.argtypes = restype, argtypes
 
     # -- helpers -------------------------------------------------------------------------------
     @staticmethod
@@ -244,21 +216,57 @@ class PinnLib:
         return (C.c_int * len(v))(*[int(x) for x in v])
 
     @staticmethod
-    def _d3(v):
-        return (C.c_double * 3)(*[float(x) for x in v])
-
-    @staticmethod
-    def _d4(v):
-        return (C.c_double * 4)(*[float(x) for x in v])
-
-    @staticmethod
     def _floats(v, n):
         v = list(v) + [0.0] * (n - len(v))
         return (C.c_float * n)(*[float(x) for x in v])
 
+    @staticmethod
+    def _box(lb, ub, normalize, dim=3):
+        """lb[dim], ub[dim], normalize"""
+        arr = C.c_double * dim
+        return arr(*[float(x) for x in lb]), arr(*[float(x) for x in ub]), int(bool(normalize))
+
+    def _net_points(self, params, layers, cols, n, lb, ub, normalize):
+        """the leading arguments of every per-point entry point: net, the 3 (x, y, t) or 4 (x, y, z, t) columns, n, box"""
+        return (params, self._ints(layers), len(layers), *cols, int(n), *self._box(lb, ub, normalize, len(cols)))
+
+    def _wave_head(self, E, mu, rho, plane_strain, term_weights):
+        return float(E), float(mu), float(rho), int(bool(plane_strain)), self._floats(term_weights, 7)
+
+    @staticmethod
+    def _tail(prec, ws, ws_bytes, stream):
+        """precision_mode, workspace, ws_bytes, stream"""
+        return mode_bits(prec), ws, int(ws_bytes), stream
+
+    @staticmethod
+    def _set_array(struct, sets):
+        """rows (x, y, t, n, targets_or_0, weights, loss_out) as a PointSet (weights: out_weights[<= 8]) or StreamSet (weights[5][<= 8]) array"""
+        arr = (struct * max(1, len(sets)))()
+        for a, (x, y, t, n, tg, w, lo) in zip(arr, sets):
+            a.x, a.y, a.t, a.n, a.targets, a.loss_terms_out = x or None, y or None, t or None, int(n), tg or None, lo
+            if struct is PointSet:
+                a.out_weights = _F8(*[float(v) for v in w[:8]])
+            else:
+                a.weights = (_F8 * 5)(*[_F8(*[float(v) for v in row]) for row in w])
+        return arr
+
+    @staticmethod
+    def adam_state(adam):
+        """None or (m, v, lr, beta1, beta2, eps, step) -> the `const pinn_adam_state*` argument"""
+        if adam is None:
+            return None
+        return C.byref(AdamState(adam[0], adam[1], float(adam[2]), float(adam[3]), float(adam[4]), float(adam[5]), int(adam[6])))
+
     def check(self, rc: int, what: str):
         if rc != 0:
-            raise PinnLibError(f"{what} failed: {self.lib.pinn_error_string(rc).decode()} (code {rc})")
+            raise PinnLibError(f"{what} failed: {self.error_string(rc)}")
+
+    def call(self, name: str, *args, accept=()) -> int:
+        """Calls the library's ``name``; a return code other than 0 or one of ``accept`` raises PinnLibError under that name"""
+        rc = getattr(self.lib, name)(*args)
+        if rc not in accept:
+            self.check(rc, name)
+        return rc
 
     def error_string(self, rc: int) -> str:
         return f"{self.lib.pinn_error_string(rc).decode()} (code {rc})"
@@ -293,21 +301,18 @@ class PinnLib:
     def path_for(self, layers, precision, head: str = "wave", ws_bytes: int = 0) -> str:
         """pinn_path_for: 'fused-registers' | 'fused-lds' | 'two-kernel' | 'fp32' for a loss + gradient call of family ``head``
         ('wave', 'data', 'plate', 'nc3d', 'nc3d_data', 'streams', 'stream_sets'); ``precision`` is a mode name or the full precision_mode word"""
-        mode = PREC[precision] if isinstance(precision, str) else int(precision)
-        rc = int(self.lib.pinn_path_for(self._ints(layers), len(layers), mode, HEADS[head], int(ws_bytes)))
+        rc = int(self.lib.pinn_path_for(self._ints(layers), len(layers), mode_bits(precision), HEADS[head], int(ws_bytes)))
         if rc <= 0:
-            raise PinnLibError(f"pinn_path_for failed: {self.lib.pinn_error_string(rc).decode()} (code {rc})")
+            raise PinnLibError(f"pinn_path_for failed: {self.error_string(rc)}")
         return PATHS[rc]
 
     def cache_policy(self, layers, head: str = "wave") -> dict:
         """pinn_debug_cache_policy: per-workgroup bytes of the fused collocation kernel's two memory classes and which of them (if any) the
         instantiation marks non-temporal -- {'policy': 'none' | 'sums' | 'images', 'images_bytes', 'sums_bytes', 'grid_bytes' (256 workgroups)}"""
         im, su = C.c_size_t(0), C.c_size_t(0)
-        self.lib.pinn_debug_cache_policy.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-        self.lib.pinn_debug_cache_policy.restype = C.c_int
         rc = int(self.lib.pinn_debug_cache_policy(self._ints(layers), len(layers), HEADS[head], C.byref(im), C.byref(su)))
         if rc < 0:
-            raise PinnLibError(f"pinn_debug_cache_policy failed: {self.lib.pinn_error_string(rc).decode()} (code {rc})")
+            raise PinnLibError(f"pinn_debug_cache_policy failed: {self.error_string(rc)}")
         return {"policy": ("none", "sums", "images")[rc], "images_bytes": int(im.value), "sums_bytes": int(su.value), "grid_bytes": 256 * (int(im.value) + int(su.value))}
 
     def path_counts(self, reset: bool = False) -> dict:
@@ -356,110 +361,70 @@ class PinnLib:
 
     def wave2d_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights,
                          loss_out, grad_out, accumulate, prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_wave2d_loss_grad(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                            int(bool(normalize)), float(E), float(mu), float(rho), int(bool(plane_strain)),
-                                            self._floats(term_weights, 7), loss_out, grad_out, int(bool(accumulate)), mode_bits(prec),
-                                            ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_wave2d_loss_grad")
+        self.call("pinn_wave2d_loss_grad", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize),
+                  *self._wave_head(E, mu, rho, plane_strain, term_weights), loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def wave2d_loss_grad_checked(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights,
                                  loss_out, grad_out, prec, ws, ws_bytes, state: "RangeState", stream=0) -> int:
         """pinn_wave2d_loss_grad_checked: the call + the finite-gradient ladder, synchronous; ``state`` is kept by the caller.  Returns the rc
         (PINN_ERR_RANGE = -7 is a result a caller may want to handle, everything else raises)."""
-        rc = self.lib.pinn_wave2d_loss_grad_checked(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                                    int(bool(normalize)), float(E), float(mu), float(rho), int(bool(plane_strain)),
-                                                    self._floats(term_weights, 7), loss_out, grad_out, mode_bits(prec), ws, int(ws_bytes), stream,
-                                                    C.byref(state))
-        if rc != -7:
-            self.check(rc, "pinn_wave2d_loss_grad_checked")
-        return rc
+        return self.call("pinn_wave2d_loss_grad_checked", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize),
+                         *self._wave_head(E, mu, rho, plane_strain, term_weights), loss_out, grad_out, *self._tail(prec, ws, ws_bytes, stream),
+                         C.byref(state), accept=(-7,))
 
     def probe_ranges(self, params, grad, n_params, ws, ws_bytes, stream=0):
         """(gradient finite?, max |w|) -- one small reduction and a stream synchronisation"""
         fin, wmax = C.c_int32(0), C.c_float(0.0)
-        self.check(self.lib.pinn_probe_ranges(params or None, grad or None, int(n_params), ws, int(ws_bytes), stream, C.byref(fin), C.byref(wmax)), "pinn_probe_ranges")
+        self.call("pinn_probe_ranges", params or None, grad or None, int(n_params), ws, int(ws_bytes), stream, C.byref(fin), C.byref(wmax))
         return bool(fin.value), float(wmax.value)
 
     def wave2d_loss_grad_profile(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights,
                                  loss_out, grad_out, accumulate, prec, ws, ws_bytes, stream=0):
         """Synchronous; returns [repack, chain, wgrad, reductions] kernel milliseconds (HIP events)."""
         ms = (C.c_float * 4)()
-        rc = self.lib.pinn_wave2d_loss_grad_profile(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb),
-                                                    self._d3(ub), int(bool(normalize)), float(E), float(mu), float(rho),
-                                                    int(bool(plane_strain)), self._floats(term_weights, 7), loss_out, grad_out,
-                                                    int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream, ms)
-        self.check(rc, "pinn_wave2d_loss_grad_profile")
+        self.call("pinn_wave2d_loss_grad_profile", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize),
+                  *self._wave_head(E, mu, rho, plane_strain, term_weights), loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream), ms)
         return [float(v) for v in ms]
 
     def data_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, targets, out_weights, loss_out, grad_out,
                        accumulate, prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_data_loss_grad(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                          int(bool(normalize)), targets, self._floats(out_weights, 8), loss_out, grad_out,
-                                          int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_data_loss_grad")
+        self.call("pinn_data_loss_grad", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), targets, self._floats(out_weights, 8),
+                  loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def data_loss_grad_multi(self, params, layers, sets, lb, ub, normalize, grad_out, accumulate, prec, ws, ws_bytes, stream=0):
         """sets: list of (x, y, t, n, targets_or_0, out_weights, loss_out) with device pointers as integers."""
-        arr = (PointSet * len(sets))()
-        for k, (x, y, t, n, tg, ow, lo) in enumerate(sets):
-            arr[k].x, arr[k].y, arr[k].t, arr[k].n, arr[k].targets, arr[k].loss_terms_out = x or None, y or None, t or None, int(n), tg or None, lo
-            for i in range(8):
-                arr[k].out_weights[i] = float(ow[i]) if i < len(ow) else 0.0
-        rc = self.lib.pinn_data_loss_grad_multi(params, self._ints(layers), len(layers), arr, len(sets), self._d3(lb), self._d3(ub),
-                                                int(bool(normalize)), grad_out, int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_data_loss_grad_multi")
+        self.call("pinn_data_loss_grad_multi", params, self._ints(layers), len(layers), self._set_array(PointSet, sets), len(sets),
+                  *self._box(lb, ub, normalize), grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def wave2d_step(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, loss_out, sets, grad_out,
                     accumulate, adam, prec, ws, ws_bytes, stream=0):
         """pinn_wave2d_step.  sets: as data_loss_grad_multi; adam: None or (m, v, lr, beta1, beta2, eps, step)."""
-        arr = (PointSet * max(1, len(sets)))()
-        for k, (sx, sy, st, sn, tg, ow, lo) in enumerate(sets):
-            arr[k].x, arr[k].y, arr[k].t, arr[k].n, arr[k].targets, arr[k].loss_terms_out = sx or None, sy or None, st or None, int(sn), tg or None, lo
-            for i in range(8):
-                arr[k].out_weights[i] = float(ow[i]) if i < len(ow) else 0.0
-        ad = None
-        if adam is not None:
-            ad = AdamState(adam[0], adam[1], float(adam[2]), float(adam[3]), float(adam[4]), float(adam[5]), int(adam[6]))
-        rc = self.lib.pinn_wave2d_step(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub), int(bool(normalize)),
-                                       float(E), float(mu), float(rho), int(bool(plane_strain)), self._floats(term_weights, 7), loss_out, arr, len(sets),
-                                       grad_out, int(bool(accumulate)), C.byref(ad) if ad is not None else None, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_wave2d_step")
+        self.call("pinn_wave2d_step", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize),
+                  *self._wave_head(E, mu, rho, plane_strain, term_weights), loss_out, self._set_array(PointSet, sets), len(sets), grad_out,
+                  int(bool(accumulate)), self.adam_state(adam), *self._tail(prec, ws, ws_bytes, stream))
 
     def plate2d_step(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, E, mu, rho, term_weights, loss_out, hx, hy, ht, hn, haux, hweights,
                      hloss_out, grad_out, accumulate, adam, prec, ws, ws_bytes, stream=0):
         """pinn_plate2d_step.  adam: None or (m, v, lr, beta1, beta2, eps, step)."""
-        ad = None
-        if adam is not None:
-            ad = AdamState(adam[0], adam[1], float(adam[2]), float(adam[3]), float(adam[4]), float(adam[5]), int(adam[6]))
-        rc = self.lib.pinn_plate2d_step(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub), int(bool(normalize)), frozen,
-                                        float(E), float(mu), float(rho), self._floats(term_weights, 5), loss_out, hx, hy, ht, int(hn), haux,
-                                        self._floats(hweights, 2), hloss_out, grad_out, int(bool(accumulate)), C.byref(ad) if ad is not None else None,
-                                        mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_plate2d_step")
+        self.call("pinn_plate2d_step", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), frozen, float(E), float(mu), float(rho),
+                  self._floats(term_weights, 5), loss_out, hx, hy, ht, int(hn), haux, self._floats(hweights, 2), hloss_out, grad_out,
+                  int(bool(accumulate)), self.adam_state(adam), *self._tail(prec, ws, ws_bytes, stream))
 
     def wave2d_fields(self, params, layers, x, y, t, n, lb, ub, normalize, fields_out, prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_wave2d_fields(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                         int(bool(normalize)), fields_out, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_wave2d_fields")
+        self.call("pinn_wave2d_fields", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), fields_out, *self._tail(prec, ws, ws_bytes, stream))
 
     def wave2d_residual_score(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, score_out, prec, ws,
                               ws_bytes, stream=0):
-        rc = self.lib.pinn_wave2d_residual_score(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                                 int(bool(normalize)), float(E), float(mu), float(rho), int(bool(plane_strain)),
-                                                 self._floats(term_weights, 7), score_out, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_wave2d_residual_score")
+        self.call("pinn_wave2d_residual_score", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize),
+                  *self._wave_head(E, mu, rho, plane_strain, term_weights), score_out, *self._tail(prec, ws, ws_bytes, stream))
 
     def wave2d_predict(self, params, layers, x, y, t, n, lb, ub, normalize, out, prec, ws, ws_bytes, stream=0):
         """pinn_wave2d_predict: out [8][n] = u, v, s11, s22, s12, e11, e22, e12"""
-        rc = self.lib.pinn_wave2d_predict(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                          int(bool(normalize)), out, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_wave2d_predict")
+        self.call("pinn_wave2d_predict", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), out, *self._tail(prec, ws, ws_bytes, stream))
 
     def plate2d_predict(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, out, prec, ws, ws_bytes, stream=0):
         """pinn_plate2d_predict: frozen [2][5][5][n] (stream rows 0..2 read), out [8][n] in the order of wave2d_predict"""
-        rc = self.lib.pinn_plate2d_predict(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                           int(bool(normalize)), frozen, out, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_plate2d_predict")
+        self.call("pinn_plate2d_predict", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), frozen, out, *self._tail(prec, ws, ws_bytes, stream))
 
     def field_error_workspace_bytes(self, n, n_rows) -> int:
         return int(self.lib.pinn_field_error_workspace_bytes(int(n), int(n_rows)))
@@ -467,113 +432,81 @@ class PinnLib:
     def field_error_sums(self, pred, pred_rows, rows, ref, n, sums_out, ws, ws_bytes, stream=0):
         """pinn_field_error_sums: sums_out (device, 2 * len(rows) doubles) = sum (pred[rows[j]] - ref[j])^2, then sum ref[j]^2"""
         rows = [int(r) for r in rows]
-        rc = self.lib.pinn_field_error_sums(pred, int(pred_rows), (C.c_int * max(1, len(rows)))(*rows), len(rows), ref, int(n), sums_out, ws,
-                                            int(ws_bytes), stream)
-        self.check(rc, "pinn_field_error_sums")
+        self.call("pinn_field_error_sums", pred, int(pred_rows), (C.c_int * max(1, len(rows)))(*rows), len(rows), ref, int(n), sums_out, ws,
+                  int(ws_bytes), stream)
 
     def select_workspace_bytes(self, n) -> int:
         return int(self.lib.pinn_select_workspace_bytes(int(n)))
 
     def select_k(self, score, n, k, largest, idx_out, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_select_k(score, int(n), int(k), int(bool(largest)), idx_out, ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_select_k")
+        self.call("pinn_select_k", score, int(n), int(k), int(bool(largest)), idx_out, ws, int(ws_bytes), stream)
 
     def sample_box(self, seed, stream_id, first, n, lo, hi, cols, stream=0):
         """pinn_sample_box.  cols: the 3 (x, y, t) or 4 (x, y, z, t) device pointers; lo / hi: as many bounds."""
         dim = len(cols)
         x, y, z, t = (cols[0], cols[1], None, cols[2]) if dim == 3 else (tuple(cols) + (None,) * 4)[:4]
         d4 = lambda v: (C.c_double * 4)(*([float(a) for a in v] + [0.0] * 4)[:4])
-        rc = self.lib.pinn_sample_box(int(seed), int(stream_id), int(first), int(n), dim, d4(lo), d4(hi), x, y, z, t, stream)
-        self.check(rc, "pinn_sample_box")
+        self.call("pinn_sample_box", int(seed), int(stream_id), int(first), int(n), dim, d4(lo), d4(hi), x, y, z, t, stream)
 
     def refine_keys_workspace_bytes(self, n) -> int:
         return int(self.lib.pinn_refine_keys_workspace_bytes(int(n)))
 
     def refine_keys(self, score, n, x, y, z, balls, mode, power, c, seed, stream_id, first, key_out, ws, ws_bytes, stream=0):
         """pinn_refine_keys.  balls: see ball_array; mode: 'mask' | 'sample'."""
-        rc = self.lib.pinn_refine_keys(score, int(n), x, y, z, ball_array(balls), len(balls), KEYS_MODE[mode], float(power), float(c), int(seed),
-                                       int(stream_id), int(first), key_out, ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_refine_keys")
+        self.call("pinn_refine_keys", score, int(n), x, y, z, ball_array(balls), len(balls), KEYS_MODE[mode], float(power), float(c), int(seed),
+                  int(stream_id), int(first), key_out, ws, int(ws_bytes), stream)
 
     def net_streams(self, params, layers, x, y, t, n, lb, ub, normalize, streams_out, prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_net_streams(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                       int(bool(normalize)), streams_out, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_net_streams")
+        self.call("pinn_net_streams", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), streams_out, *self._tail(prec, ws, ws_bytes, stream))
 
     def plate2d_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, E, mu, rho, term_weights, loss_out, grad_out,
                           accumulate, prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_plate2d_loss_grad(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                             int(bool(normalize)), frozen, float(E), float(mu), float(rho),
-                                             self._floats(term_weights, 5), loss_out, grad_out, int(bool(accumulate)), mode_bits(prec),
-                                             ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_plate2d_loss_grad")
+        self.call("pinn_plate2d_loss_grad", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), frozen, float(E), float(mu), float(rho),
+                  self._floats(term_weights, 5), loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def plate2d_residual_score(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, E, mu, rho, term_weights, score_out, prec, ws, ws_bytes,
                                stream=0):
-        rc = self.lib.pinn_plate2d_residual_score(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                                  int(bool(normalize)), frozen, float(E), float(mu), float(rho), self._floats(term_weights, 5),
-                                                  score_out, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_plate2d_residual_score")
+        self.call("pinn_plate2d_residual_score", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), frozen, float(E), float(mu),
+                  float(rho), self._floats(term_weights, 5), score_out, *self._tail(prec, ws, ws_bytes, stream))
 
     def nc3d_residual_score(self, params, layers, x, y, z, t, n, lb, ub, normalize, E, mu, rho, term_weights, score_out, prec, ws, ws_bytes,
                             stream=0):
-        rc = self.lib.pinn_nc3d_residual_score(params, self._ints(layers), len(layers), x, y, z, t, int(n), self._d4(lb), self._d4(ub),
-                                               int(bool(normalize)), float(E), float(mu), float(rho), self._floats(term_weights, 12), score_out,
-                                               mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_nc3d_residual_score")
+        self.call("pinn_nc3d_residual_score", *self._net_points(params, layers, (x, y, z, t), n, lb, ub, normalize), float(E), float(mu), float(rho),
+                  self._floats(term_weights, 12), score_out, *self._tail(prec, ws, ws_bytes, stream))
 
     def plate2d_traction_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, aux, weights, loss_out, grad_out, accumulate,
                                    prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_plate2d_traction_loss_grad(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb),
-                                                      self._d3(ub), int(bool(normalize)), aux, self._floats(weights, 2), loss_out,
-                                                      grad_out, int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_plate2d_traction_loss_grad")
+        self.call("pinn_plate2d_traction_loss_grad", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), aux, self._floats(weights, 2),
+                  loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def stream_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, targets, weights, loss_out, grad_out, accumulate, prec,
                          ws, ws_bytes, stream=0):
         w = [float(v) for row in weights for v in row]
-        rc = self.lib.pinn_stream_loss_grad(params, self._ints(layers), len(layers), x, y, t, int(n), self._d3(lb), self._d3(ub),
-                                            int(bool(normalize)), targets, (C.c_float * len(w))(*w), loss_out, grad_out,
-                                            int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_stream_loss_grad")
+        self.call("pinn_stream_loss_grad", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), targets, (C.c_float * len(w))(*w),
+                  loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def stream_loss_grad_multi(self, params, layers, sets, lb, ub, normalize, grad_out, accumulate, prec, ws, ws_bytes, stream=0):
         """pinn_stream_loss_grad_multi.  sets: list of (x, y, t, n, targets_or_0, weights[5][<=8], loss_out) with device pointers as
         integers; the reported sums of every set are normalised by the largest |weight| of the whole call."""
-        arr = (StreamSet * max(1, len(sets)))()
-        for k, (x, y, t, n, tg, w, lo) in enumerate(sets):
-            arr[k].x, arr[k].y, arr[k].t, arr[k].n, arr[k].targets, arr[k].loss_terms_out = x or None, y or None, t or None, int(n), tg or None, lo
-            for s_, row in enumerate(w):
-                for o, v in enumerate(row):
-                    arr[k].weights[s_][o] = float(v)
-        rc = self.lib.pinn_stream_loss_grad_multi(params, self._ints(layers), len(layers), arr, len(sets), self._d3(lb), self._d3(ub),
-                                                  int(bool(normalize)), grad_out, int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_stream_loss_grad_multi")
+        self.call("pinn_stream_loss_grad_multi", params, self._ints(layers), len(layers), self._set_array(StreamSet, sets), len(sets),
+                  *self._box(lb, ub, normalize), grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     # -- 3-D Navier-Cauchy extension (4 inputs x, y, z, t; 12 outputs) ---------------------------------------------
     def nc3d_loss_grad(self, params, layers, x, y, z, t, n, lb, ub, normalize, E, mu, rho, term_weights, loss_out, grad_out, accumulate,
                        prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_nc3d_loss_grad(params, self._ints(layers), len(layers), x, y, z, t, int(n), self._d4(lb), self._d4(ub),
-                                          int(bool(normalize)), float(E), float(mu), float(rho), self._floats(term_weights, 12), loss_out,
-                                          grad_out, int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_nc3d_loss_grad")
+        self.call("pinn_nc3d_loss_grad", *self._net_points(params, layers, (x, y, z, t), n, lb, ub, normalize), float(E), float(mu), float(rho),
+                  self._floats(term_weights, 12), loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def nc3d_data_loss_grad(self, params, layers, x, y, z, t, n, lb, ub, normalize, targets, out_weights, loss_out, grad_out, accumulate,
                             prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_nc3d_data_loss_grad(params, self._ints(layers), len(layers), x, y, z, t, int(n), self._d4(lb), self._d4(ub),
-                                               int(bool(normalize)), targets, self._floats(out_weights, 16), loss_out, grad_out,
-                                               int(bool(accumulate)), mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_nc3d_data_loss_grad")
+        self.call("pinn_nc3d_data_loss_grad", *self._net_points(params, layers, (x, y, z, t), n, lb, ub, normalize), targets,
+                  self._floats(out_weights, 16), loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
 
     def nc3d_fields(self, params, layers, x, y, z, t, n, lb, ub, normalize, fields_out, prec, ws, ws_bytes, stream=0):
-        rc = self.lib.pinn_nc3d_fields(params, self._ints(layers), len(layers), x, y, z, t, int(n), self._d4(lb), self._d4(ub),
-                                       int(bool(normalize)), fields_out, mode_bits(prec), ws, int(ws_bytes), stream)
-        self.check(rc, "pinn_nc3d_fields")
+        self.call("pinn_nc3d_fields", *self._net_points(params, layers, (x, y, z, t), n, lb, ub, normalize), fields_out, *self._tail(prec, ws, ws_bytes, stream))
 
     def adam_step(self, params, m, v, grad, n_params, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, stream=0):
-        rc = self.lib.pinn_adam_step(params, m, v, grad, int(n_params), float(lr), float(beta1), float(beta2), float(eps),
-                                     int(step), stream)
-        self.check(rc, "pinn_adam_step")
+        self.call("pinn_adam_step", params, m, v, grad, int(n_params), float(lr), float(beta1), float(beta2), float(eps), int(step), stream)
 
     # -- L-BFGS on the device (pinn_lbfgs_*) ---------------------------------------------------------------------------
     def lbfgs_state_bytes(self, n_params: int, history: int) -> int:
@@ -584,22 +517,22 @@ class PinnLib:
         o = LbfgsOptions(int(options.get("maxcor", 10)), int(options.get("maxiter", 15000)), int(options.get("maxfun", 15000)), int(options.get("maxls", 20)),
                          float(options.get("ftol", 2.220446049250313e-09)), float(options.get("gtol", 1e-5)))
         c = [float(v) for v in loss_coeffs]
-        self.check(self.lib.pinn_lbfgs_init(state or None, int(state_bytes), int(n_params), C.byref(o), (C.c_float * max(1, len(c)))(*c), len(c),
-                                            float(grad_scale), stream), "pinn_lbfgs_init")
+        self.call("pinn_lbfgs_init", state or None, int(state_bytes), int(n_params), C.byref(o), (C.c_float * max(1, len(c)))(*c), len(c),
+                  float(grad_scale), stream)
 
     def lbfgs_advance(self, state, params, grad, sums, stream=0):
-        self.check(self.lib.pinn_lbfgs_advance(state or None, params or None, grad or None, sums or None, stream), "pinn_lbfgs_advance")
+        self.call("pinn_lbfgs_advance", state or None, params or None, grad or None, sums or None, stream)
 
     def lbfgs_status(self, state, stream=0) -> dict:
         """pinn_lbfgs_status (synchronises the stream): the record as a dict, with 'status_name' from LBFGS_STATUS"""
         r = LbfgsRecord()
-        self.check(self.lib.pinn_lbfgs_status(state or None, C.byref(r), stream), "pinn_lbfgs_status")
+        self.call("pinn_lbfgs_status", state or None, C.byref(r), stream)
         return r.as_dict()
 
     def lbfgs_read_losses(self, state, first: int, count: int, stream=0):
         """losses of the evaluations [first, first + count) as a list of floats (synchronises)"""
         out = (C.c_double * max(1, int(count)))()
-        self.check(self.lib.pinn_lbfgs_read_losses(state or None, int(first), int(count), out, stream), "pinn_lbfgs_read_losses")
+        self.call("pinn_lbfgs_read_losses", state or None, int(first), int(count), out, stream)
         return [float(v) for v in out[:int(count)]]
 
     def lbfgs_debug_read(self, state, n_params: int, history: int, stream=0):
@@ -609,6 +542,6 @@ class PinnLib:
         S = _np.zeros((int(history), int(n_params)), dtype=_np.float32)
         Y = _np.zeros_like(S)
         n = C.c_int(0)
-        self.check(self.lib.pinn_lbfgs_debug_read(state or None, int(n_params), int(history), d.ctypes.data, S.ctypes.data, Y.ctypes.data, int(history),
-                                                  C.byref(n), stream), "pinn_lbfgs_debug_read")
+        self.call("pinn_lbfgs_debug_read", state or None, int(n_params), int(history), d.ctypes.data, S.ctypes.data, Y.ctypes.data, int(history),
+                  C.byref(n), stream)
         return d, S[:n.value].copy(), Y[:n.value].copy()

@@ -5,6 +5,7 @@ GPU or without the built shared library, construction raises.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Sequence
 
 import torch
@@ -16,6 +17,12 @@ def param_count(layers: Sequence[int]) -> int:
     return sum(layers[i] * layers[i + 1] + layers[i + 1] for i in range(len(layers) - 1))
 
 
+def aligned_buffer(nbytes: int, device):
+    """(byte tensor, pointer): ``nbytes`` behind a 256-byte aligned pointer, what every workspace and state argument of include/pinn_hip.h asks for"""
+    buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+    return buf, (buf.data_ptr() + 255) // 256 * 256
+
+
 class LbfgsState:
     """The caller-owned state buffer of pinn_lbfgs_* (include/pinn_hip.h): a byte tensor and its 256-byte aligned window"""
 
@@ -24,8 +31,7 @@ class LbfgsState:
         self.nbytes = lib.lbfgs_state_bytes(n_params, history)
         if self.nbytes == 0:
             raise PinnLibError(f"no L-BFGS state for n_params={n_params}, history={history} (history must be 1..64)")
-        self.buf = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=device)
-        self.ptr = (self.buf.data_ptr() + 255) // 256 * 256
+        self.buf, self.ptr = aligned_buffer(self.nbytes, device)
 
 
 class LbfgsMixin:
@@ -90,11 +96,8 @@ class HipEngine(LbfgsMixin):
         if want == 0:
             raise PinnLibError(f"no kernel variant for layers={self.layers} precision={precision}")
         self.ws_bytes = int(want)
-        self.ws = torch.empty(self.ws_bytes + 256, dtype=torch.uint8, device=self.device)
-        self._ws_ptr = (self.ws.data_ptr() + 255) // 256 * 256
-
+        self.ws, self._ws_ptr = aligned_buffer(self.ws_bytes, self.device)
         self._lib_path = lib_path
-        self._err_ws = None                   # workspace of field_error_sums, allocated at its first call
 
     def for_layers(self, layers: Sequence[int]) -> "HipEngine":
         """A sibling engine for a net of other layer sizes (same precision mode, device and library): neural_net(X, weights, biases) of
@@ -106,8 +109,12 @@ class HipEngine(LbfgsMixin):
         """precision_mode argument of the loss / gradient calls: the precision, PINN_FLAG_WEIGHTS_PACKED when the previous call of this
         engine used the same parameter values (skip the repack launch), and the current adjoint shift (``self.adjoint_shift``, see
         PINN_ADJOINT_SHIFT in include/pinn_hip.h; the model classes adapt it when a gradient comes back non-finite)."""
-        return (PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0) | (FLAG_STATE_FP16 if self.fast_state else 0)
+        return (self._forward_mode(packed) | (FLAG_STATE_FP16 if self.fast_state else 0)
                 | (FLAG_TWO_KERNEL if self.two_kernel else 0) | adjoint_shift(self.adjoint_shift))
+
+    def _forward_mode(self, packed: bool) -> int:
+        """precision_mode argument of the forward-only score and predict calls: the precision and PINN_FLAG_WEIGHTS_PACKED, no other flag"""
+        return PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0)
 
     def leave_fused_path_if_weights_out_of_range(self, params: torch.Tensor) -> bool:
         """The fused kernels' weight format holds |w| <= 2047 (include/pinn_hip.h); beyond it a call returns NaN throughout.  Called by the
@@ -142,75 +149,119 @@ class HipEngine(LbfgsMixin):
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    # ---- argument marshalling shared by the methods below -------------------------------------------------------------
     @staticmethod
     def _chk(t: torch.Tensor, n: Optional[int] = None):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "expect contiguous fp32 device tensors"
         if n is not None:
             assert t.numel() == n, f"expected {n} elements, got {t.numel()}"
 
+    def _check(self, params, cols) -> int:
+        """The checks of every method that takes point columns (x, y, t) or (x, y, z, t): contiguous fp32 device tensors of one length, and
+        ``params`` one of n_params elements.  Returns the number of points."""
+        n = cols[0].numel()
+        for v in cols:
+            self._chk(v, n)
+        self._chk(params, self.n_params)
+        return n
+
+    def _optional(self, t: Optional[torch.Tensor], numel: int) -> int:
+        """pointer of an optional tensor of ``numel`` elements (targets), 0 for None"""
+        if t is None:
+            return 0
+        self._chk(t, numel)
+        return t.data_ptr()
+
+    def _net(self, params, cols, n, lb, ub, normalize):
+        """the leading arguments of a capi.PinnLib per-point call"""
+        return (params.data_ptr(), self.layers, *[v.data_ptr() for v in cols], n, lb, ub, normalize)
+
+    def _ws_tail(self):
+        return self._ws_ptr, self.ws_bytes, self._stream()
+
+    def _grad(self, grad_out, accumulate):
+        if grad_out is None:
+            return torch.empty(self.n_params, dtype=torch.float32, device=self.device), False
+        return grad_out, accumulate
+
+    def _outs(self, grad_out, accumulate, loss_out, n_loss: int = 8):
+        grad_out, accumulate = self._grad(grad_out, accumulate)
+        if loss_out is None:
+            loss_out = torch.empty(n_loss, dtype=torch.float32, device=self.device)
+        return grad_out, accumulate, loss_out
+
+    def _new_or_checked(self, out, shape):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self._chk(out, math.prod(shape))
+        return out
+
+    def _set_rows(self, sets, per_point: int, min_loss: int = 0):
+        """side sets (x, y, t, targets [per_point * n] or None, weights, loss_out) -> the rows capi.PinnLib takes; ``min_loss``: the
+        loss_out tensors are checked to hold that many floats"""
+        rows = []
+        for x, y, t, tg, w, lo in sets:
+            n = x.numel()
+            for v in (x, y, t):
+                self._chk(v, n)
+            if min_loss:
+                assert lo.is_cuda and lo.dtype == torch.float32 and lo.is_contiguous() and lo.numel() >= min_loss
+            rows.append((x.data_ptr(), y.data_ptr(), t.data_ptr(), n, self._optional(tg, per_point * n), w, lo.data_ptr()))
+        return rows
+
+    def _adam(self, adam):
+        """adam = (m, v, lr, step[, beta1, beta2, eps]) or None -> the (m, v, lr, beta1, beta2, eps, step) of capi.PinnLib or None"""
+        if adam is None:
+            return None
+        m, v, lr, step = adam[:4]
+        b1, b2, eps = (list(adam[4:]) + [0.9, 0.999, 1e-8][len(adam) - 4:])[:3]
+        for a in (m, v):
+            self._chk(a, self.n_params)
+        return m.data_ptr(), v.data_ptr(), lr, b1, b2, eps, step
+
+    def _scratch(self, name: str, nbytes_of):
+        """(pointer, bytes) of the scratch buffer ``name`` of a call family whose size does not depend on n: allocated at its first use, one per engine"""
+        if name not in self.__dict__:
+            nbytes = nbytes_of()
+            buf, ptr = aligned_buffer(nbytes, self.device)
+            self.__dict__.update({name: buf, name + "_ptr": ptr, name + "_bytes": nbytes})
+        return self.__dict__[name + "_ptr"], self.__dict__[name + "_bytes"]
+
+    # ---- wave family (4 streams: value, d/dx, d/dy, d/dt) ---------------------------------------------------------------
     def wave_loss_grad(self, params, x, y, t, lb, ub, normalize, term_weights, E=2.5, mu=0.25, rho=1.0, plane_strain=True,
                        grad_out: Optional[torch.Tensor] = None, accumulate: bool = False, loss_out: Optional[torch.Tensor] = None, packed: bool = False):
         """Returns (sumsq[7] device tensor, grad_flat).  grad = d/dparams sum_i term_weights[i]*sumsq[i]."""
-        n = x.numel()
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        if grad_out is None:
-            grad_out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            accumulate = False
-        if loss_out is None:
-            loss_out = torch.empty(8, dtype=torch.float32, device=self.device)
-        self.lib.wave2d_loss_grad(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                                  E, mu, rho, plane_strain, term_weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate,
-                                  self._mode(packed), self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, t))
+        grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out)
+        self.lib.wave2d_loss_grad(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, term_weights,
+                                  loss_out.data_ptr(), grad_out.data_ptr(), accumulate, self._mode(packed), *self._ws_tail())
         return loss_out[:7], grad_out
 
     def wave_loss_grad_profile(self, params, x, y, t, lb, ub, normalize, term_weights, E=2.5, mu=0.25, rho=1.0, plane_strain=True):
         """Synchronous variant returning HIP-event kernel times in ms: dict(repack, chain, wgrad, reduce)."""
-        n = x.numel()
-        grad = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        loss = torch.empty(8, dtype=torch.float32, device=self.device)
-        ms = self.lib.wave2d_loss_grad_profile(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub,
-                                               normalize, E, mu, rho, plane_strain, term_weights, loss.data_ptr(), grad.data_ptr(),
-                                               False, self.precision, self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, t))
+        grad, _, loss = self._outs(None, False, None)
+        ms = self.lib.wave2d_loss_grad_profile(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, term_weights,
+                                               loss.data_ptr(), grad.data_ptr(), False, self.precision, *self._ws_tail())
         return dict(zip(("repack", "chain", "wgrad", "reduce"), ms))
 
     def data_loss_grad(self, params, x, y, t, lb, ub, normalize, targets, out_weights,
                        grad_out: Optional[torch.Tensor] = None, accumulate: bool = False, loss_out: Optional[torch.Tensor] = None, packed: bool = False):
         """Value-only terms.  targets: [n_out, n] device tensor or None.  Returns (sumsq[n_out], grad)."""
-        n = x.numel()
-        nout = self.layers[-1]
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        tptr = 0
-        if targets is not None:
-            self._chk(targets, nout * n)
-            tptr = targets.data_ptr()
-        if grad_out is None:
-            grad_out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            accumulate = False
-        if loss_out is None:
-            loss_out = torch.empty(8, dtype=torch.float32, device=self.device)
-        self.lib.data_loss_grad(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                                tptr, out_weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate, self._mode(packed),
-                                self._ws_ptr, self.ws_bytes, self._stream())
+        n, nout = self._check(params, (x, y, t)), self.layers[-1]
+        tptr = self._optional(targets, nout * n)
+        grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out)
+        self.lib.data_loss_grad(*self._net(params, (x, y, t), n, lb, ub, normalize), tptr, out_weights, loss_out.data_ptr(), grad_out.data_ptr(),
+                                accumulate, self._mode(packed), *self._ws_tail())
         return loss_out[:nout], grad_out
 
     def data_loss_grad_multi(self, params, sets, lb, ub, normalize, grad_out, accumulate=False, packed=False):
         """Several value-only sets in one call.  sets: list of (x, y, t, targets_or_None, out_weights, loss_out[>=n_out]); the sums of
         set k land in its loss_out, the gradients are summed into grad_out."""
         self._chk(params, self.n_params)
-        rows = []
-        for x, y, t, tg, ow, lo in sets:
-            n = x.numel()
-            for v in (x, y, t):
-                self._chk(v, n)
-            if tg is not None:
-                self._chk(tg, self.layers[-1] * n)
-            rows.append((x.data_ptr(), y.data_ptr(), t.data_ptr(), n, 0 if tg is None else tg.data_ptr(), ow, lo.data_ptr()))
+        rows = self._set_rows(sets, self.layers[-1])
         self.lib.data_loss_grad_multi(params.data_ptr(), self.layers, rows, lb, ub, normalize, grad_out.data_ptr(), accumulate, self._mode(packed),
-                                      self._ws_ptr, self.ws_bytes, self._stream())
+                                      *self._ws_tail())
         return grad_out
 
     def wave_step(self, params, x, y, t, lb, ub, normalize, term_weights, sets, grad_out, loss_out, E=2.5, mu=0.25, rho=1.0, plane_strain=True,
@@ -220,41 +271,18 @@ class HipEngine(LbfgsMixin):
         ``grad_out`` and -- with ``adam = (m, v, lr, step[, beta1, beta2, eps])`` -- the TF1 Adam update of ``params`` behind it.  For the nets of
         the register-state fused kernel that is repack | one persistent launch | one reduction (+ Adam); for every other net the library makes
         the separate calls inside: the same bits either way."""
-        n = x.numel()
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
+        n = self._check(params, (x, y, t))
         self._chk(grad_out, self.n_params)
-        rows = []
-        for sx, sy, st, tg, ow, lo in sets:
-            m_ = sx.numel()
-            for v in (sx, sy, st):
-                self._chk(v, m_)
-            if tg is not None:
-                self._chk(tg, self.layers[-1] * m_)
-            rows.append((sx.data_ptr(), sy.data_ptr(), st.data_ptr(), m_, 0 if tg is None else tg.data_ptr(), ow, lo.data_ptr()))
-        ad = None
-        if adam is not None:
-            m, v, lr, step = adam[:4]
-            b1, b2, eps = (list(adam[4:]) + [0.9, 0.999, 1e-8][len(adam) - 4:])[:3]
-            for a_ in (m, v):
-                self._chk(a_, self.n_params)
-            ad = (m.data_ptr(), v.data_ptr(), lr, b1, b2, eps, step)
-        self.lib.wave2d_step(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, E, mu, rho, plane_strain,
-                             term_weights, loss_out.data_ptr(), rows, grad_out.data_ptr(), accumulate, ad, self._mode(False), self._ws_ptr, self.ws_bytes,
-                             self._stream())
+        rows = self._set_rows(sets, self.layers[-1])
+        self.lib.wave2d_step(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, term_weights, loss_out.data_ptr(), rows,
+                             grad_out.data_ptr(), accumulate, self._adam(adam), self._mode(False), *self._ws_tail())
         return grad_out
 
     def fields(self, params, x, y, t, lb, ub, normalize):
         """Returns [4, n_out, n]: Y and its derivatives w.r.t. x, y, t."""
-        n = x.numel()
-        nout = self.layers[-1]
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        out = torch.empty((4, nout, n), dtype=torch.float32, device=self.device)
-        self.lib.wave2d_fields(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                               out.data_ptr(), self.precision, self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, t))
+        out = torch.empty((4, self.layers[-1], n), dtype=torch.float32, device=self.device)
+        self.lib.wave2d_fields(*self._net(params, (x, y, t), n, lb, ub, normalize), out.data_ptr(), self.precision, *self._ws_tail())
         return out
 
     # ---- residual-adaptive refinement: per-point score and selection ------------------------------------------------
@@ -262,81 +290,49 @@ class HipEngine(LbfgsMixin):
                        out: Optional[torch.Tensor] = None, packed: bool = False):
         """Returns the device tensor [n] of  sum_i term_weights[i] * f_i(n)^2  (pinn_wave2d_residual_score): the wave residuals of
         net_f_sig per point, formed in the kernel -- nothing but the score leaves it."""
-        n = x.numel()
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=self.device)
-        self._chk(out, n)
-        self.lib.wave2d_residual_score(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, E, mu, rho,
-                                       plane_strain, term_weights, out.data_ptr(), PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0),
-                                       self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, t))
+        out = self._new_or_checked(out, (n,))
+        self.lib.wave2d_residual_score(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, term_weights, out.data_ptr(),
+                                       self._forward_mode(packed), *self._ws_tail())
         return out
 
     def plate_residual_score(self, params, x, y, t, lb, ub, normalize, frozen, term_weights, E=20.0, mu=0.25, rho=1.0,
                              out: Optional[torch.Tensor] = None, packed: bool = False):
         """The same for the plate family (pinn_plate2d_residual_score): ``frozen`` is the [2, 5, 5, n] tensor of plate_loss_grad at these points,
         the five residuals are those of the composite P + D*N.  Returns the device tensor [n]."""
-        n = x.numel()
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
+        n = self._check(params, (x, y, t))
         self._chk(frozen, 50 * n)
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=self.device)
-        self._chk(out, n)
-        self.lib.plate2d_residual_score(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                                        frozen.data_ptr(), E, mu, rho, term_weights, out.data_ptr(),
-                                        PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr, self.ws_bytes, self._stream())
+        out = self._new_or_checked(out, (n,))
+        self.lib.plate2d_residual_score(*self._net(params, (x, y, t), n, lb, ub, normalize), frozen.data_ptr(), E, mu, rho, term_weights, out.data_ptr(),
+                                        self._forward_mode(packed), *self._ws_tail())
         return out
 
     def nc3d_residual_score(self, params, x, y, z, t, lb, ub, normalize, term_weights, E=2.5, mu=0.25, rho=1.0,
                             out: Optional[torch.Tensor] = None, packed: bool = False):
         """The same for the 4-input family (pinn_nc3d_residual_score): the twelve residuals of nc3d_loss_grad.  Returns the device tensor [n]."""
-        n = x.numel()
-        for v in (x, y, z, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=self.device)
-        self._chk(out, n)
-        self.lib.nc3d_residual_score(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), z.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                                     E, mu, rho, term_weights, out.data_ptr(), PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr,
-                                     self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, z, t))
+        out = self._new_or_checked(out, (n,))
+        self.lib.nc3d_residual_score(*self._net(params, (x, y, z, t), n, lb, ub, normalize), E, mu, rho, term_weights, out.data_ptr(),
+                                     self._forward_mode(packed), *self._ws_tail())
         return out
 
     # ---- predict heads: value + space tangents only, and the per-field error sums behind them ------------------------
-    def _predict_out(self, rows, n, out):
-        if out is None:
-            out = torch.empty((rows, n), dtype=torch.float32, device=self.device)
-        self._chk(out, rows * n)
-        return out
-
     def wave_predict(self, params, x, y, t, lb, ub, normalize, out: Optional[torch.Tensor] = None, packed: bool = False):
         """Returns the device tensor [8, n] = u, v, s11, s22, s12, e11, e22, e12 (pinn_wave2d_predict): the forward of ``fields`` with the
         streams value, d/dx, d/dy only -- no time tangent."""
-        n = x.numel()
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        out = self._predict_out(8, n, out)
-        self.lib.wave2d_predict(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, out.data_ptr(),
-                                PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, t))
+        out = self._new_or_checked(out, (8, n))
+        self.lib.wave2d_predict(*self._net(params, (x, y, t), n, lb, ub, normalize), out.data_ptr(), self._forward_mode(packed), *self._ws_tail())
         return out
 
     def plate_predict(self, params, x, y, t, lb, ub, normalize, frozen, out: Optional[torch.Tensor] = None, packed: bool = False):
         """The same for the plate family (pinn_plate2d_predict): ``frozen`` is the [2, 5, 5, n] tensor of plate_loss_grad at these points (its
         stream rows 0..2 are read), the eight rows are those of the composite P + D*N."""
-        n = x.numel()
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
+        n = self._check(params, (x, y, t))
         self._chk(frozen, 50 * n)
-        out = self._predict_out(8, n, out)
-        self.lib.plate2d_predict(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, frozen.data_ptr(),
-                                 out.data_ptr(), PREC[self.precision] | (FLAG_WEIGHTS_PACKED if packed else 0), self._ws_ptr, self.ws_bytes,
-                                 self._stream())
+        out = self._new_or_checked(out, (8, n))
+        self.lib.plate2d_predict(*self._net(params, (x, y, t), n, lb, ub, normalize), frozen.data_ptr(), out.data_ptr(), self._forward_mode(packed),
+                                 *self._ws_tail())
         return out
 
     def field_error_sums(self, pred, rows, ref, out: Optional[torch.Tensor] = None):
@@ -346,30 +342,22 @@ class HipEngine(LbfgsMixin):
         rows = [int(r) for r in rows]
         n = pred.shape[-1]
         self._chk(ref, len(rows) * n)
-        if self._err_ws is None:            # (the size depends on the row count only: one buffer per engine, for the 16 rows a call may have)
-            nbytes = self.lib.field_error_workspace_bytes(0, 16)
-            self._err_ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            self._err_ws_ptr, self._err_ws_bytes = (self._err_ws.data_ptr() + 255) // 256 * 256, nbytes
+        # (the size depends on the row count only: one buffer for the 16 rows a call may have)
+        ws, ws_bytes = self._scratch("_err_ws", lambda: self.lib.field_error_workspace_bytes(0, 16))
         if out is None:
             out = torch.empty((2, len(rows)), dtype=torch.float64, device=self.device)
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 2 * len(rows)
         self.lib.field_error_sums(pred.data_ptr(), pred.numel() // n if n else max(rows) + 1, rows, ref.data_ptr(), n, out.data_ptr(),
-                                  self._err_ws_ptr, self._err_ws_bytes, self._stream())
+                                  ws, ws_bytes, self._stream())
         return out
 
     def select_k(self, score, k: int, largest: bool = True):
         """The k largest (or smallest) entries of the device tensor ``score`` as a device int32 [k] of ASCENDING indices (pinn_select_k):
         ties go to the lowest index, a NaN ranks above +inf, the result is exactly reproducible.  No synchronisation."""
         self._chk(score)
-        n = score.numel()
-        ws = self.__dict__.get("_select_ws")
-        if ws is None:                      # (the size does not depend on n: one buffer per engine)
-            nbytes = self.lib.select_workspace_bytes(0)
-            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            self._select_ws = ws
-            self._select_ws_ptr, self._select_ws_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
+        ws, ws_bytes = self._scratch("_select_ws", lambda: self.lib.select_workspace_bytes(0))
         out = torch.empty(int(k), dtype=torch.int32, device=self.device)
-        self.lib.select_k(score.data_ptr(), n, k, largest, out.data_ptr(), self._select_ws_ptr, self._select_ws_bytes, self._stream())
+        self.lib.select_k(score.data_ptr(), score.numel(), k, largest, out.data_ptr(), ws, ws_bytes, self._stream())
         return out
 
     def sample_box(self, n: int, lo, hi, seed: int, stream: int = 0, first: int = 0):
@@ -388,48 +376,29 @@ class HipEngine(LbfgsMixin):
         n = score.numel()
         for v in cols:
             self._chk(v, n)
-        ws = self.__dict__.get("_keys_ws")
-        if ws is None:                      # (the size does not depend on n: one buffer per engine)
-            nbytes = self.lib.refine_keys_workspace_bytes(0)
-            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-            self._keys_ws = ws
-            self._keys_ws_ptr, self._keys_ws_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
+        ws, ws_bytes = self._scratch("_keys_ws", lambda: self.lib.refine_keys_workspace_bytes(0))
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         x, y = (cols[0].data_ptr(), cols[1].data_ptr()) if len(cols) >= 2 else (None, None)      # (no columns: fine without balls)
         z = cols[2].data_ptr() if len(cols) == 4 else None
-        self.lib.refine_keys(score.data_ptr(), n, x, y, z, list(balls), mode, power, c, seed, stream, first,
-                             out.data_ptr(), self._keys_ws_ptr, self._keys_ws_bytes, self._stream())
+        self.lib.refine_keys(score.data_ptr(), n, x, y, z, list(balls), mode, power, c, seed, stream, first, out.data_ptr(), ws, ws_bytes, self._stream())
         return out
 
     # ---- plate family (5 streams: value, d/dx, d/dy, d/dt, d2/dt2) --------------------------------------------------
     def net_streams(self, params, x, y, t, lb, ub, normalize):
         """Returns [5, n_out, n]: the net's outputs, their first derivatives and the second time derivative."""
-        n, nout = x.numel(), self.layers[-1]
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        out = torch.empty((5, nout, n), dtype=torch.float32, device=self.device)
-        self.lib.net_streams(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                             out.data_ptr(), self.precision, self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, t))
+        out = torch.empty((5, self.layers[-1], n), dtype=torch.float32, device=self.device)
+        self.lib.net_streams(*self._net(params, (x, y, t), n, lb, ub, normalize), out.data_ptr(), self.precision, *self._ws_tail())
         return out
-
-    def _outs(self, grad_out, accumulate, loss_out):
-        if grad_out is None:
-            grad_out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            accumulate = False
-        if loss_out is None:
-            loss_out = torch.empty(8, dtype=torch.float32, device=self.device)
-        return grad_out, accumulate, loss_out
 
     def plate_loss_grad(self, params, x, y, t, lb, ub, normalize, frozen, term_weights, E=20.0, mu=0.25, rho=1.0,
                         grad_out=None, accumulate=False, loss_out=None):
         """frozen: [2, 5, 5, n] streams of the distance and particular nets.  Returns (sumsq[5], grad wrt this net)."""
-        n = x.numel()
+        n = self._check(params, (x, y, t))
         self._chk(frozen, 50 * n)
         grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out)
-        self.lib.plate2d_loss_grad(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                                   frozen.data_ptr(), E, mu, rho, term_weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate,
-                                   self._mode(False), self._ws_ptr, self.ws_bytes, self._stream())
+        self.lib.plate2d_loss_grad(*self._net(params, (x, y, t), n, lb, ub, normalize), frozen.data_ptr(), E, mu, rho, term_weights,
+                                   loss_out.data_ptr(), grad_out.data_ptr(), accumulate, self._mode(False), *self._ws_tail())
         return loss_out[:5], grad_out
 
     def plate_step(self, params, x, y, t, lb, ub, normalize, frozen, term_weights, hole, grad_out, loss_out, hole_loss_out, E=20.0, mu=0.25, rho=1.0,
@@ -437,45 +406,33 @@ class HipEngine(LbfgsMixin):
         """The plate's step in one library call (pinn_plate2d_step): collocation set (frozen: [2, 5, 5, n]) + hole-traction set
         ``hole = (x, y, t, aux[12, n], weights[2])`` -> gradient in ``grad_out``, sums in ``loss_out`` / ``hole_loss_out``, and with
         ``adam = (m, v, lr, step[, beta1, beta2, eps])`` the TF1 Adam update of ``params`` in the same final launch."""
-        n = x.numel()
-        for v in (x, y, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
+        n = self._check(params, (x, y, t))
         self._chk(frozen, 50 * n)
+        self._chk(grad_out, self.n_params)
         hx, hy, ht, haux, hw = hole
-        hn = hx.numel()
+        hn = self._check(params, (hx, hy, ht))
         self._chk(haux, 12 * hn)
-        ad = None
-        if adam is not None:
-            m, v, lr, step = adam[:4]
-            b1, b2, eps = (list(adam[4:]) + [0.9, 0.999, 1e-8][len(adam) - 4:])[:3]
-            ad = (m.data_ptr(), v.data_ptr(), lr, b1, b2, eps, step)
-        self.lib.plate2d_step(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, frozen.data_ptr(), E, mu, rho,
-                              term_weights, loss_out.data_ptr(), hx.data_ptr(), hy.data_ptr(), ht.data_ptr(), hn, haux.data_ptr(), hw, hole_loss_out.data_ptr(),
-                              grad_out.data_ptr(), accumulate, ad, self._mode(False), self._ws_ptr, self.ws_bytes, self._stream())
+        self.lib.plate2d_step(*self._net(params, (x, y, t), n, lb, ub, normalize), frozen.data_ptr(), E, mu, rho, term_weights, loss_out.data_ptr(),
+                              hx.data_ptr(), hy.data_ptr(), ht.data_ptr(), hn, haux.data_ptr(), hw, hole_loss_out.data_ptr(), grad_out.data_ptr(),
+                              accumulate, self._adam(adam), self._mode(False), *self._ws_tail())
         return grad_out
 
     def traction_loss_grad(self, params, x, y, t, lb, ub, normalize, aux, weights, grad_out=None, accumulate=False, loss_out=None, packed=False):
         """aux: [12, n] = D values, P values, nx, ny.  Returns ((sum tx^2, sum ty^2), grad)."""
-        n = x.numel()
+        n = self._check(params, (x, y, t))
         self._chk(aux, 12 * n)
         grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out)
-        self.lib.plate2d_traction_loss_grad(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub,
-                                            normalize, aux.data_ptr(), weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate,
-                                            self._mode(packed), self._ws_ptr, self.ws_bytes, self._stream())
+        self.lib.plate2d_traction_loss_grad(*self._net(params, (x, y, t), n, lb, ub, normalize), aux.data_ptr(), weights, loss_out.data_ptr(),
+                                            grad_out.data_ptr(), accumulate, self._mode(packed), *self._ws_tail())
         return loss_out[:2], grad_out
 
     def stream_loss_grad(self, params, x, y, t, lb, ub, normalize, targets, weights, grad_out=None, accumulate=False, loss_out=None):
         """targets: [5, n_out, n] or None; weights: 5 x n_out nested list.  Returns (per-output normalised sums, grad)."""
-        n, nout = x.numel(), self.layers[-1]
-        tptr = 0
-        if targets is not None:
-            self._chk(targets, 5 * nout * n)
-            tptr = targets.data_ptr()
+        n, nout = self._check(params, (x, y, t)), self.layers[-1]
+        tptr = self._optional(targets, 5 * nout * n)
         grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out)
-        self.lib.stream_loss_grad(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), t.data_ptr(), n, lb, ub, normalize, tptr,
-                                  weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate, self.precision, self._ws_ptr,
-                                  self.ws_bytes, self._stream())
+        self.lib.stream_loss_grad(*self._net(params, (x, y, t), n, lb, ub, normalize), tptr, weights, loss_out.data_ptr(), grad_out.data_ptr(),
+                                  accumulate, self.precision, *self._ws_tail())
         return loss_out[:nout], grad_out
 
     def stream_loss_grad_multi(self, params, sets, lb, ub, normalize, grad_out=None, accumulate=False):
@@ -484,71 +441,38 @@ class HipEngine(LbfgsMixin):
         by the largest |weight| of ALL sets; the gradient of the unnormalised loss goes to grad_out.  Returns grad_out."""
         self._chk(params, self.n_params)
         nout = self.layers[-1]
-        rows = []
-        for x, y, t, tg, w, lo in sets:
-            n = x.numel()
-            for v in (x, y, t):
-                self._chk(v, n)
-            if tg is not None:
-                self._chk(tg, 5 * nout * n)
-            assert lo.is_cuda and lo.dtype == torch.float32 and lo.is_contiguous() and lo.numel() >= nout
-            rows.append((x.data_ptr(), y.data_ptr(), t.data_ptr(), n, 0 if tg is None else tg.data_ptr(), w, lo.data_ptr()))
-        if grad_out is None:
-            grad_out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            accumulate = False
+        rows = self._set_rows(sets, 5 * nout, min_loss=nout)
+        grad_out, accumulate = self._grad(grad_out, accumulate)
         self._chk(grad_out, self.n_params)
         self.lib.stream_loss_grad_multi(params.data_ptr(), self.layers, rows, lb, ub, normalize, grad_out.data_ptr(), accumulate, self._mode(False),
-                                        self._ws_ptr, self.ws_bytes, self._stream())
+                                        *self._ws_tail())
         return grad_out
 
     # ---- 3-D Navier-Cauchy extension (layers [4, H, ..., H, 12]; inputs x, y, z, t) -------------------------------------
     def nc3d_loss_grad(self, params, x, y, z, t, lb, ub, normalize, term_weights, E=2.5, mu=0.25, rho=1.0,
                        grad_out=None, accumulate=False, loss_out=None, packed=False):
         """Returns (sumsq[12], grad): residuals (f_u,f_v,f_w,f_ut,f_vt,f_wt,f_s11,f_s22,f_s33,f_s12,f_s13,f_s23), see include/pinn_hip.h."""
-        n = x.numel()
-        for v in (x, y, z, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        if grad_out is None:
-            grad_out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            accumulate = False
-        if loss_out is None:
-            loss_out = torch.empty(16, dtype=torch.float32, device=self.device)
-        self.lib.nc3d_loss_grad(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), z.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                                E, mu, rho, term_weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate, self._mode(packed),
-                                self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, z, t))
+        grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out, 16)
+        self.lib.nc3d_loss_grad(*self._net(params, (x, y, z, t), n, lb, ub, normalize), E, mu, rho, term_weights, loss_out.data_ptr(),
+                                grad_out.data_ptr(), accumulate, self._mode(packed), *self._ws_tail())
         return loss_out[:12], grad_out
 
     def nc3d_data_loss_grad(self, params, x, y, z, t, lb, ub, normalize, targets, out_weights,
                             grad_out=None, accumulate=False, loss_out=None, packed=False):
         """Value-only terms of the 4-input net.  targets: [n_out, n] device tensor or None.  Returns (sumsq[n_out], grad)."""
-        n, nout = x.numel(), self.layers[-1]
-        for v in (x, y, z, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        tptr = 0
-        if targets is not None:
-            self._chk(targets, nout * n)
-            tptr = targets.data_ptr()
-        if grad_out is None:
-            grad_out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-            accumulate = False
-        if loss_out is None:
-            loss_out = torch.empty(16, dtype=torch.float32, device=self.device)
-        self.lib.nc3d_data_loss_grad(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), z.data_ptr(), t.data_ptr(), n, lb, ub,
-                                     normalize, tptr, out_weights, loss_out.data_ptr(), grad_out.data_ptr(), accumulate,
-                                     self._mode(packed), self._ws_ptr, self.ws_bytes, self._stream())
+        n, nout = self._check(params, (x, y, z, t)), self.layers[-1]
+        tptr = self._optional(targets, nout * n)
+        grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out, 16)
+        self.lib.nc3d_data_loss_grad(*self._net(params, (x, y, z, t), n, lb, ub, normalize), tptr, out_weights, loss_out.data_ptr(),
+                                     grad_out.data_ptr(), accumulate, self._mode(packed), *self._ws_tail())
         return loss_out[:nout], grad_out
 
     def nc3d_fields(self, params, x, y, z, t, lb, ub, normalize):
         """Returns [5, n_out, n]: the outputs and their derivatives w.r.t. x, y, z, t."""
-        n, nout = x.numel(), self.layers[-1]
-        for v in (x, y, z, t):
-            self._chk(v, n)
-        self._chk(params, self.n_params)
-        out = torch.empty((5, nout, n), dtype=torch.float32, device=self.device)
-        self.lib.nc3d_fields(params.data_ptr(), self.layers, x.data_ptr(), y.data_ptr(), z.data_ptr(), t.data_ptr(), n, lb, ub, normalize,
-                             out.data_ptr(), self.precision, self._ws_ptr, self.ws_bytes, self._stream())
+        n = self._check(params, (x, y, z, t))
+        out = torch.empty((5, self.layers[-1], n), dtype=torch.float32, device=self.device)
+        self.lib.nc3d_fields(*self._net(params, (x, y, z, t), n, lb, ub, normalize), out.data_ptr(), self.precision, *self._ws_tail())
         return out
 
     def adam_step(self, params, m, v, grad, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):

@@ -10,7 +10,7 @@ from typing import Optional
 
 import torch
 
-from .capi import AdamState, PinnLib, PinnLibError
+from .capi import PinnLib, PinnLibError
 
 HANDLE_BYTES = 128     # PINN_IPC_HANDLE_BYTES: hipIpcMemHandle_t + memory kind + PCI bus id of the owning device
 
@@ -27,16 +27,6 @@ class P2PAllReduce:
         self.rank = torch.distributed.get_rank(group)
         self.world = torch.distributed.get_world_size(group)
         L = lib.lib
-        L.pinn_p2p_create.argtypes = [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.c_void_p]
-        L.pinn_p2p_connect.argtypes = [C.c_void_p, C.c_void_p]
-        L.pinn_p2p_allreduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(AdamState), C.c_int64, C.c_void_p]
-        L.pinn_p2p_status.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-        L.pinn_p2p_peek_status.argtypes = [C.c_void_p]
-        L.pinn_p2p_set_timeout_ms.argtypes = [C.c_void_p, C.c_double]
-        L.pinn_p2p_destroy.argtypes = [C.c_void_p]
-        for f in (L.pinn_p2p_create, L.pinn_p2p_connect, L.pinn_p2p_allreduce, L.pinn_p2p_status, L.pinn_p2p_peek_status, L.pinn_p2p_set_timeout_ms,
-                  L.pinn_p2p_destroy):
-            f.restype = C.c_int
         self._comm = C.c_void_p()
         handle = (C.c_ubyte * HANDLE_BYTES)()
         # Every rank takes part in BOTH exchanges whatever happened to it locally, and all ranks raise together: a rank that raised before the
@@ -58,7 +48,7 @@ class P2PAllReduce:
             raise PinnLibError(f"pinn_p2p_connect failed on rank(s) {bad}: {lib.error_string(bad[0][1])} "
                                "(PINN_ERR_COLLECTIVE here: a coarse-grained receive buffer across two devices -- use collective='rccl')")
         if timeout_s is not None:
-            lib.check(L.pinn_p2p_set_timeout_ms(self._comm, 1e3 * float(timeout_s)), "pinn_p2p_set_timeout_ms")
+            lib.call("pinn_p2p_set_timeout_ms", self._comm, 1e3 * float(timeout_s))
         self.max_floats = int(max_floats)
 
     def _destroy(self):
@@ -74,17 +64,15 @@ class P2PAllReduce:
         if adam is not None:
             params, m, v, lr, step = adam[:5]
             b1, b2, eps = (list(adam[5:]) + [0.9, 0.999, 1e-8][len(adam) - 5:])[:3]
-            ad = AdamState(m.data_ptr(), v.data_ptr(), float(lr), float(b1), float(b2), float(eps), int(step))
+            ad = (m.data_ptr(), v.data_ptr(), lr, b1, b2, eps, step)
             params_ptr = params.data_ptr()
         stream = torch.cuda.current_stream(buf.device).cuda_stream
-        self.lib.check(self.lib.lib.pinn_p2p_allreduce(self._comm, buf.data_ptr(), buf.numel(), params_ptr, C.byref(ad) if ad is not None else None,
-                                                       int(n_params), stream), "pinn_p2p_allreduce")
+        self.lib.call("pinn_p2p_allreduce", self._comm, buf.data_ptr(), buf.numel(), params_ptr, self.lib.adam_state(ad), int(n_params), stream)
 
     def status(self) -> dict:
         """synchronises; raises if a rank did not arrive within the bounded wait of some call"""
         fg = C.c_int(0)
-        rc = self.lib.lib.pinn_p2p_status(self._comm, C.byref(fg))
-        self.lib.check(rc, "pinn_p2p_status")
+        self.lib.call("pinn_p2p_status", self._comm, C.byref(fg))
         return {"fine_grained": bool(fg.value), "world": self.world, "rank": self.rank}
 
     def check(self) -> None:

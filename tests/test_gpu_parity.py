@@ -115,8 +115,10 @@ def test_fused_matches_two_kernel_path(dev):
         lib.set_fused(False)
         l2, g2 = eng.wave_loss_grad(theta, *xs, LB, UB, True, tw)
         torch.cuda.synchronize()
+        ms = eng.wave_loss_grad_profile(theta, *xs, LB, UB, True, tw)      # (synchronous; on this path the weight gradient is a kernel of its own)
     finally:
         lib.set_fused(True)
+    assert set(ms) == {"repack", "chain", "wgrad", "reduce"} and ms["chain"] > 0 and ms["wgrad"] > 0 and min(ms.values()) >= 0, ms
     assert rel(l1.cpu().numpy(), l2.cpu().numpy()) < 1e-6
     assert rel(g1.cpu().numpy(), g2.cpu().numpy()) < 1e-4
 
