@@ -211,6 +211,48 @@ int pinn_wave2d_predict(const float* params_flat, const int* layers, int n_layer
                         const double lb[3], const double ub[3], int normalize,
                         float* out, int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
+/* What the collocation data say about the material constants: fp64 sums over a point set of the wave residuals' squares and of their products
+ * with the streams they are linear in.  net_f_sig (INF:221-265) is linear in the Hooke coefficients (c1, c2, G) and in rho, so the derivative
+ * of a collocation loss by each of them is a moment sum of quantities the forward pass already carries -- no reverse pass.
+ *   sums_out  DEVICE array of PINN_MATERIAL_SUMS doubles:
+ *     k = 0..6 :  sum_n f_k(n)^2,  k in (f_u, f_v, f_ut, f_vt, f_s11, f_s22, f_s12)      (what the loss call reports, here in fp64)
+ *     k = 7    :  sum_n f_s11 * e11        e11 = du/dx,  e22 = dv/dy,  e12 = du/dy + dv/dx   (INF:216-218)
+ *     k = 8    :  sum_n f_s11 * e22
+ *     k = 9    :  sum_n f_s22 * e11
+ *     k = 10   :  sum_n f_s22 * e22
+ *     k = 11   :  sum_n f_s12 * e12
+ *     k = 12   :  sum_n f_u * d(ut)/dt
+ *     k = 13   :  sum_n f_v * d(vt)/dt
+ *   For a loss L = sum_i w_i sum_n f_i(n)^2 (w in the order of k = 0..6), with M_k = sums_out[k]:
+ *     dL/dc1  = -2 (w4 M7 + w5 M10)        dL/dc2  = -2 (w4 M8 + w5 M9)
+ *     dL/dG   = -2 w6 M11                  dL/drho = -2 (w0 M12 + w1 M13)
+ *   No weights enter the call: the sums are raw.  The chain rule from (c1, c2, G) to (E, mu) in either plane mode is the caller's.
+ * Forward only: the four streams of pinn_wave2d_fields and the residuals as pinn_wave2d_residual_score forms them (fp32); squares, products and
+ * every addition in fp64.  Determinism: one record of partial sums per wave of the launch, written in a fixed place, then one workgroup adds the
+ * records in index order -- no floating-point atomics; the sums are a function of the arguments alone.  Every compiled family (all widths and
+ * operand modes, any depth) and PINN_PREC_FP32 (which walks the points in passes and adds the passes' totals in pass order);
+ * pinn_min_workspace_bytes() is enough for any n; honours PINN_FLAG_WEIGHTS_PACKED; not a loss + gradient call: pinn_debug_path_counts does not
+ * count it.  No host synchronisation; n == 0 writes zeros.
+ * `sums_workspace` is device memory of pinn_material_sums_workspace_bytes() bytes (the partial records of the largest launch), 256-byte aligned;
+ * it is scratch of the call.
+ * Errors: layers not ending in 7 outputs: PINN_ERR_LAYERS; n < 0: PINN_ERR_SIZE; a NULL array that is needed: PINN_ERR_NULL; either workspace
+ * short or misaligned: PINN_ERR_WORKSPACE.
+ * Accuracy: the forward is the one of pinn_wave2d_fields in the same mode; on top of it the head rounds at most
+ * 8 eps32 * sum_n a_i(n)^2 (k < 7) or 8 eps32 * sum_n a_i(n) |g(n)| (k >= 7), a_i = the sum of the absolute values of the terms of f_i, g the
+ * second factor (measured: <= 0.16 of that bound in every family, 1 to 300 001 points).  Against the float64 sums, max_k |error_k| / S_k
+ * (S_k = bound_k / (8 eps32); never |sum_k|: the moment sums cancel at a trained net) over 1000 collocation points as a multiple of the same
+ * error of the sums evaluated in float32 on the host (MI355X): f16x3 2.2 / 4.6 / 1.7 at fresh 4x32, fresh 8x64 and the reference's trained 8x80
+ * net, PINN_PREC_FP32 0.8 / 0.4 / 1.3.  Timing (the score call's, within 4 %) and the cost in training: profiles/material_sums_calls.txt. */
+#define PINN_MATERIAL_SUMS 14
+size_t pinn_material_sums_workspace_bytes(void);
+int pinn_wave2d_material_sums(const float* params_flat, const int* layers, int n_layers,
+                              const float* x, const float* y, const float* t, int64_t n,
+                              const double lb[3], const double ub[3], int normalize,
+                              double E, double mu, double rho, int plane_strain,
+                              double* sums_out,
+                              int precision_mode, void* workspace, size_t ws_bytes,
+                              void* sums_workspace, size_t sums_ws_bytes, void* stream);
+
 /* Per-field error sums of a predict output against reference data on the device: what the relative L2 comparison with FEM frames needs
  * (sqrt(sums[0][j] / sums[1][j]) per field), without downloading the fields.
  *   pred      DEVICE array [pred_rows][n], e.g. the output of a predict call

@@ -49,6 +49,7 @@ class StreamSet(C.Structure):
 
 
 MAX_BALLS = 4                      # PINN_MAX_BALLS
+MATERIAL_SUMS = 14                 # PINN_MATERIAL_SUMS
 KEYS_MODE = {"mask": 0, "sample": 1}             # PINN_KEYS_*
 
 
@@ -134,6 +135,8 @@ PROTOTYPES = {
     "pinn_wave2d_fields": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
     "pinn_wave2d_residual_score": (_i32, _NET + _PTS3 + _WAVE + [_vp] + _TAIL),
     "pinn_wave2d_predict": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
+    "pinn_material_sums_workspace_bytes": (_sz, []),
+    "pinn_wave2d_material_sums": (_i32, _NET + _PTS3 + _MAT + [_i32, _vp] + _TAIL[:3] + [_vp, _sz, _vp]),
     "pinn_field_error_workspace_bytes": (_sz, [_i64, _i32]),
     "pinn_field_error_sums": (_i32, [_vp, _i64, _pi32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "pinn_select_workspace_bytes": (_sz, [_i64]),
@@ -425,6 +428,16 @@ class PinnLib:
     def plate2d_predict(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, out, prec, ws, ws_bytes, stream=0):
         """pinn_plate2d_predict: frozen [2][5][5][n] (stream rows 0..2 read), out [8][n] in the order of wave2d_predict"""
         self.call("pinn_plate2d_predict", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), frozen, out, *self._tail(prec, ws, ws_bytes, stream))
+
+    def material_sums_workspace_bytes(self) -> int:
+        return int(self.lib.pinn_material_sums_workspace_bytes())
+
+    def wave2d_material_sums(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, sums_out, prec, ws, ws_bytes,
+                             sums_ws, sums_ws_bytes, stream=0):
+        """pinn_wave2d_material_sums: sums_out (device, MATERIAL_SUMS doubles) = the seven sums of squared wave residuals, then the seven
+        moment sums of include/pinn_hip.h; sums_ws: material_sums_workspace_bytes() of scratch"""
+        self.call("pinn_wave2d_material_sums", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), float(E), float(mu), float(rho),
+                  int(bool(plane_strain)), sums_out, *self._tail(prec, ws, ws_bytes, stream)[:3], sums_ws, int(sums_ws_bytes), stream)
 
     def field_error_workspace_bytes(self, n, n_rows) -> int:
         return int(self.lib.pinn_field_error_workspace_bytes(int(n), int(n_rows)))

@@ -347,7 +347,7 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
     a.head = head;
     a.din = din;
     a.second = (din == 3 && ns == 5) ? 1 : 0;
-    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head) || head_is_predict(head);
+    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head) || head_is_predict(head) || head == HEAD_MATERIAL;
     int pass = 0;
     for (long p0 = 0; p0 < c.n; p0 += mmax, ++pass) {
         a.p0 = p0;
@@ -363,7 +363,9 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
             hipLaunchKernelGGL(fp32_sum_kernel, dim3(nterms), dim3(256), 0, st, (const float*)a.fsq, a.m, c.loss_out, pass > 0 ? 1 : 0);
             hipLaunchKernelGGL(fp32_wgrad_kernel, dim3((c.net.nparams + 255) / 256), dim3(256), 0, st, a, c.grad_out, (c.accumulate || pass > 0) ? 1 : 0);
         }
-        const int rc = (int)hipGetLastError();
+        int rc = (int)hipGetLastError();
+        // pinn_wave2d_material_sums: the pass's 14 term rows added in fp64, its total into the sums in pass order
+        if (!rc && head == HEAD_MATERIAL) rc = material::launch_fp32_pass(a.fsq, a.m, c.moment_part, c.moment_out, pass, st);
         if (rc) return rc;
     }
     return PINN_OK;
@@ -627,6 +629,29 @@ int pinn_wave2d_predict(const float* params_flat, const int* layers, int n_layer
     if (n > 0 && !out) return PINN_ERR_NULL;
     if (c.net.nout != 7) return PINN_ERR_LAYERS;
     return run_forward(c, impl, out, &Impl::wave_predict, HEAD_PREDICT, 3);
+}
+
+size_t pinn_material_sums_workspace_bytes(void) { return align_up(material::ws_bytes(), 256); }
+
+int pinn_wave2d_material_sums(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
+                              int64_t n, const double lb[3], const double ub[3], int normalize, double E, double mu, double rho,
+                              int plane_strain, double* sums_out, int precision_mode, void* workspace, size_t ws_bytes, void* sums_workspace,
+                              size_t sums_ws_bytes, void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (!sums_out || !sums_workspace) return PINN_ERR_NULL;
+    if (c.net.nout != 7) return PINN_ERR_LAYERS;
+    if (((uintptr_t)sums_workspace & 255) != 0 || sums_ws_bytes < pinn_material_sums_workspace_bytes()) return PINN_ERR_WORKSPACE;
+    set_hooke(c, E, mu, rho, plane_strain);
+    c.moment_part = static_cast<double*>(sums_workspace);
+    c.moment_out = sums_out;
+    if (c.n == 0) return (int)hipMemsetAsync(sums_out, 0, PINN_MATERIAL_SUMS * sizeof(double), c.stream);      // an empty set: zero sums
+    static_assert(PINN_MATERIAL_SUMS == MATERIAL_SUMS, "sums of the header and of the head");
+    static_assert(FP32_TERMS >= MATERIAL_SUMS, "term rows of a PINN_PREC_FP32 pass");
+    if (!impl) return fp32_call(c, HEAD_MATERIAL, 0, 4, 3, false);
+    return impl->wave_material(c);
 }
 
 size_t pinn_field_error_workspace_bytes(int64_t n, int n_rows) {

@@ -250,8 +250,13 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 //               (The 4-input family has no such head: value + x, y, z are four streams, and the four-stream instantiations of padded width 128
 //               -- HEAD_SCORE's too -- spill registers where the five-stream ones fit, so at the 10 x 128 net it measured slower than
 //               HEAD_FIELDS3D: 4.83 against 4.64 ms per 1 M points.)
+// HEAD_MATERIAL: forward only, 4 streams: the wave residuals once more, reduced to MATERIAL_SUMS fp64 sums over the points -- the seven sums of
+//               squares and the seven moment sums the derivatives of the collocation loss by (c1, c2, G, rho) are made of, the residuals being
+//               linear in those four (pinn_wave2d_material_sums).  One record of MATERIAL_SUMS doubles per wave through `moment_part`; a second
+//               launch (pinn_material.hpp) adds the records in index order.  No weights, no per-point output.
 enum { HEAD_WAVE = 0, HEAD_DATA = 1, HEAD_FIELDS = 2, HEAD_PLATE = 3, HEAD_TRACTION = 4, HEAD_STREAMS = 5, HEAD_NC3D = 6, HEAD_DATA3D = 7,
-       HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11, HEAD_PREDICT = 12, HEAD_PREDICT_PLATE = 13 };
+       HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11, HEAD_PREDICT = 12, HEAD_PREDICT_PLATE = 13, HEAD_MATERIAL = 14 };
+constexpr int MATERIAL_SUMS = 14;     // HEAD_MATERIAL: sums per record (PINN_MATERIAL_SUMS)
 __host__ __device__ constexpr bool head_is_3d(int head) {
     return head == HEAD_NC3D || head == HEAD_DATA3D || head == HEAD_FIELDS3D || head == HEAD_SCORE3D;
 }
@@ -281,6 +286,7 @@ struct ChainArgs {
     float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  score heads: [n];  predict heads: [8][n]
     const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_PREDICT_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
     float w5[5][8];            // HEAD_STREAMS: per (stream, output) weights, max-normalised
+    double* moment_part;       // HEAD_MATERIAL: [total waves][MATERIAL_SUMS] per-wave sums
 };
 
 struct WgradArgs {
@@ -717,13 +723,17 @@ struct Chain {
         const int wpb = blockDim.x >> 6;
         const long gwave = (long)blockIdx.x * wpb + (threadIdx.x >> 6), nwaves = (long)gridDim.x * wpb;
         const int nl = a.net.nl;
-        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD) || head_is_predict(HEAD);
+        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD) || head_is_predict(HEAD) || HEAD == HEAD_MATERIAL;
         constexpr bool SPILL = !FWD_ONLY;
         __shared__ __attribute__((aligned(16))) char spill_lds[4 * 1024];      // one 1 KB transpose record per wave (256-thread blocks)
         char* rec = spill_lds + (threadIdx.x >> 6) * 1024;
         float lsum[LT];
 #pragma unroll
         for (int i = 0; i < LT; ++i) lsum[i] = 0.0f;
+        constexpr int MS = HEAD == HEAD_MATERIAL ? MATERIAL_SUMS : 1;
+        double msum[MS];      // HEAD_MATERIAL: the lane's sums over every tile of the wave (q == 0 lanes hold a point)
+#pragma unroll
+        for (int k = 0; k < MS; ++k) msum[k] = 0.0;
 
         for (long tile = gwave; tile < a.ntiles; tile += nwaves) {
             uint16_t* St = SPILL ? a.S + tile * a.S_tile_stride : nullptr;
@@ -1044,6 +1054,39 @@ struct Chain {
 #pragma unroll
                     for (int i = 0; i < 7; ++i) sc += a.tw[i] * (f[i] * f[i]);
                     if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
+                } else if constexpr (HEAD == HEAD_MATERIAL) {
+                    // the seven residuals once more (a third copy of HEAD_WAVE's lines, net_f_sig INF:221-265: the loss kernels' code does not
+                    // move), formed in fp32; their squares and their products with the strain / acceleration streams they are linear in are
+                    // exact in fp64 and added per lane.  A padded lane (valid[nb] false: it re-read point n - 1) adds nothing.
+                    const float(&V)[8] = Y[0][nb];
+                    const float(&X)[8] = Y[1][nb];
+                    const float(&Yy)[8] = Y[2][nb];
+                    const float(&T)[8] = Y[3][nb];
+                    const float e11 = X[0], e22 = Yy[1], e12 = Yy[0] + X[1];          // INF:216-218
+                    float f[7];
+                    f[0] = X[4] + Yy[6] - a.rho * T[2];                               // f_u   INF:262
+                    f[1] = Yy[5] + X[6] - a.rho * T[3];                               // f_v   INF:263
+                    f[2] = T[0] - V[2];                                               // f_ut  INF:248
+                    f[3] = T[1] - V[3];                                               // f_vt  INF:249
+                    f[4] = V[4] - (a.c1 * e11 + a.c2 * e22);                          // f_s11 INF:244
+                    f[5] = V[5] - (a.c2 * e11 + a.c1 * e22);                          // f_s22 INF:246
+                    f[6] = V[6] - a.G * e12;                                          // f_s12 INF:245
+                    if (q == 0 && valid[nb]) {
+                        double fd[7];
+#pragma unroll
+                        for (int i = 0; i < 7; ++i) {
+                            fd[i] = (double)f[i];
+                            msum[i] += fd[i] * fd[i];
+                        }
+                        const double d11 = (double)e11, d22 = (double)e22;
+                        msum[7] += fd[4] * d11;
+                        msum[8] += fd[4] * d22;
+                        msum[9] += fd[5] * d11;
+                        msum[10] += fd[5] * d22;
+                        msum[11] += fd[6] * (double)e12;
+                        msum[12] += fd[0] * (double)T[2];
+                        msum[13] += fd[1] * (double)T[3];
+                    }
                 } else if constexpr (HEAD == HEAD_SCORE_PLATE) {
                     // the plate's score: composite F = P + D*N and the five residuals exactly as HEAD_PLATE forms them (PLATE:383-387,
                     // 404-439), a second copy like HEAD_SCORE's; outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt)
@@ -1209,6 +1252,18 @@ struct Chain {
                 v += __shfl_xor(v, 4);
                 v += __shfl_xor(v, 8);
                 if (lane == 0) a.loss_part[gwave * LT + i] = v;
+            }
+        }
+        if constexpr (HEAD == HEAD_MATERIAL) {
+            // the wave's record: a fixed tree over the 16 point lanes (q == 0), written by lane 0; a wave without tiles writes zeros
+#pragma unroll
+            for (int k = 0; k < MATERIAL_SUMS; ++k) {
+                double v = msum[k];
+                v += __shfl_xor(v, 1);
+                v += __shfl_xor(v, 2);
+                v += __shfl_xor(v, 4);
+                v += __shfl_xor(v, 8);
+                if (lane == 0) a.moment_part[gwave * MATERIAL_SUMS + k] = v;
             }
         }
     }

@@ -157,6 +157,28 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             a.fields_out[gp] = sc;
             continue;
         }
+        if (a.head == HEAD_MATERIAL) {
+            // pinn_wave2d_material_sums: the seven residuals (the lines of HEAD_WAVE below), their squares and their products with the streams
+            // they are linear in, one fp32 row each of the pass's `fsq` buffer; material::fp32_partial_kernel adds the rows in fp64
+            const float e11 = Y[1][0], e22 = Y[2][1], e12 = Y[2][0] + Y[1][1];
+            float f[7];
+            f[0] = Y[1][4] + Y[2][6] - a.rho * Y[3][2];
+            f[1] = Y[2][5] + Y[1][6] - a.rho * Y[3][3];
+            f[2] = Y[3][0] - Y[0][2];
+            f[3] = Y[3][1] - Y[0][3];
+            f[4] = Y[0][4] - (a.c1 * e11 + a.c2 * e22);
+            f[5] = Y[0][5] - (a.c2 * e11 + a.c1 * e22);
+            f[6] = Y[0][6] - a.G * e12;
+            for (int i = 0; i < 7; ++i) a.fsq[(long)i * a.m + p] = f[i] * f[i];
+            a.fsq[7L * a.m + p] = f[4] * e11;
+            a.fsq[8L * a.m + p] = f[4] * e22;
+            a.fsq[9L * a.m + p] = f[5] * e11;
+            a.fsq[10L * a.m + p] = f[5] * e22;
+            a.fsq[11L * a.m + p] = f[6] * e12;
+            a.fsq[12L * a.m + p] = f[0] * Y[3][2];
+            a.fsq[13L * a.m + p] = f[1] * Y[3][3];
+            continue;
+        }
         if (a.head == HEAD_SCORE_PLATE) {
             // pinn_plate2d_residual_score: the composite and the five residuals of HEAD_PLATE below, sum_i tw[i] f_i^2 through fields_out
             float D[5][5], F[5][5];

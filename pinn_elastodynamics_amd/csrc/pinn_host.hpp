@@ -9,6 +9,7 @@
 #include "../../include/pinn_hip.h"
 #include "pinn_device.hpp"
 #include "pinn_fused.hpp"
+#include "pinn_material.hpp"
 
 namespace pinn {
 
@@ -79,6 +80,9 @@ struct Call {
     DataSet sets[4];
     // fields head
     float* fields_out;
+    // material head (pinn_wave2d_material_sums): per-wave records, MATERIAL_SUMS doubles each, and the 14 sums
+    double* moment_part = nullptr;
+    double* moment_out = nullptr;
     // plate / traction / stream-target heads
     const float* aux;
     float w5[5][8];
@@ -130,6 +134,8 @@ struct Impl {
     // predict heads (forward only, value + space tangents): HEAD_PREDICT every compiled line; HEAD_PREDICT_PLATE split modes only
     int (*wave_predict)(const Call&);
     int (*plate_predict)(const Call&);
+    // the fp64 residual and moment sums of the wave family (forward only, HEAD_MATERIAL + the one-workgroup final pass)
+    int (*wave_material)(const Call&);
     // pinn_debug_cache_policy: the collocation kernel compiled for this net and head (asked of the F16 split-3 line of the net's width)
     int (*cache_policy)(const NetDesc&, int head, size_t* images_bytes, size_t* sums_bytes);
 };
@@ -439,6 +445,7 @@ struct Host {
         a.targets = c.targets;
         a.fields_out = c.fields_out;
         a.aux = c.aux;
+        a.moment_part = c.moment_part;
         for (int i = 0; i < 5; ++i)
             for (int o = 0; o < 8; ++o) a.w5[i][o] = 0.0f;
         a.S = nullptr;
@@ -815,12 +822,14 @@ struct Host {
     // Forward only, one launch of the chain kernel with a head that writes per point (c.fields_out): the fields and streams (output weights
     // zeroed) and the residual scores (with_tw: c.tw as given).  No panels, so the fixed part of the plan is all the workspace it needs; not a
     // loss + gradient call: no path counter.
+    template <int NB>
+    static long forward_tiles(long n) { return (((n + 16 * NB - 1) / (16 * NB)) + 1) & ~1L; }
     template <int NS, int HEAD, int NB = nb<NS>()>
     static int forward(const Call& c, bool with_tw) {
         Plan p;
         int rc = make_plan<NS>(c, p, false);      // (no panels: only the fixed part of this plan is used -- its offsets and fixed_end do not depend on NS)
         if (rc) return rc;
-        const long ntiles = (((c.n + 16 * NB - 1) / (16 * NB)) + 1) & ~1L;      // tiles of THIS launch's block count (the plan's belong to nb<NS>())
+        const long ntiles = forward_tiles<NB>(c.n);      // tiles of THIS launch's block count (the plan's belong to nb<NS>())
         rc = repack(c, p);
         if (rc) return rc;
         ChainArgs a;
@@ -848,6 +857,16 @@ struct Host {
     static int nc3d_score(const Call& c) {
         if constexpr (SPLIT == 3) return forward<5, HEAD_SCORE3D>(c, true);
         return PINN_ERR_PRECISION;
+    }
+
+    // pinn_wave2d_material_sums: every wave of the chain launch writes its record (one without tiles writes zeros), then one workgroup adds
+    // the records in index order
+    static int wave_material(const Call& c) {
+        const int rc = forward<4, HEAD_MATERIAL>(c, false);
+        if (rc) return rc;
+        const int nrecords = chain_blocks(forward_tiles<nb<4>()>(c.n)) * 4;
+        static_assert(MAX_BLOCKS * 4 <= material::MAX_RECORDS, "records of the largest chain grid");
+        return material::launch_final(c.moment_part, nrecords, c.moment_out, 0, c.stream);
     }
 
     // 5-stream family (plate): split-precision variants only
@@ -985,7 +1004,7 @@ struct Host {
         static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
                                &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
                                &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score,
-                               &wave_predict, &plate_predict, &cache_policy};
+                               &wave_predict, &plate_predict, &wave_material, &cache_policy};
         return &I;
     }
 };

@@ -20,6 +20,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import material
 from .model_base import ShardedSetsModel
 from .net_api import write_checkpoint
 # (the optimizer and parameter helpers lived in this module before optim.py: tools and tests import them from here)
@@ -168,6 +169,49 @@ class DeepHPM(ShardedSetsModel, PredictMixin):
         C = Candidates(self, candidates, 3, "(x, y, t)", select, power, c, seed, stream, box, exclude)
         return refine_sharded_set(self, C, n_replace, self._score_weights(weights), ("x_c", "y_c", "t_c"))
 
+    # ------------------------------------------------------------------------------------------
+    # identification of E, mu, rho: the moment sums of the collocation residuals (material.py)
+    # ------------------------------------------------------------------------------------------
+    def _material_weights(self, n_blk):
+        """what _loss_and_grad puts on the seven collocation terms of a block of ``n_blk`` points"""
+        return [self.layout["f_uv"] / n_blk] * 4 + [self.layout["f_s"] / n_blk] * 3
+
+    def _material_sums_device(self, lo, hi, packed=False):
+        """the 14 sums of engine.material_sums over the rows [lo, hi) of the collocation set as a float64 tensor on the engine's device: this
+        rank's rows, then summed over the process group by torch.distributed.all_reduce (whatever ``collective`` is: the P2P kernel is for the
+        gradient buffer).  No host synchronisation."""
+        s, e = self._shard(lo, hi)
+        if e > s:
+            x, y, t = self._rows(lo, hi)
+            kw = {"packed": True} if packed else {}
+            sums = self.engine.material_sums(self.theta, x, y, t, self.lb, self.ub, self.normalize, self.E, self.mu, self.rho, True, **kw)
+        else:
+            sums = torch.zeros(material.N_SUMS, dtype=torch.float64, device=self.device)
+        if self._reduce:
+            torch.distributed.all_reduce(sums, group=self.pg)
+        return sums
+
+    def _material_sums_async(self, lo, hi, packed=False):
+        """_material_sums_device on its way to the host: returns fetch() -> numpy [14], which waits for nothing enqueued after this call"""
+        if self.device.type == "cuda" and not hasattr(self, "_material_pinned"):
+            self._material_pinned = material.pinned_sums()
+        return material.sums_to_host(self._material_sums_device(lo, hi, packed), getattr(self, "_material_pinned", None))
+
+    def material_sums(self, idx_start=0, idx_end=None):
+        """The 14 sums of pinn_wave2d_material_sums (include/pinn_hip.h) over the rows [idx_start, idx_end) of the collocation set -- default:
+        the whole set -- at the current weights and constants, host numpy [14]: the seven sums of squared residuals of net_f_sig, then the seven
+        moment sums.  Data parallel: every rank computes its shard's rows and gets the total."""
+        hi = self._n_collo if idx_end is None else int(idx_end)
+        out = self._material_sums_async(int(idx_start), hi)()
+        self._check_collective()
+        return out
+
+    def material_gradient(self, weights=None):
+        """dict(E, mu, rho) -> the derivative of the collocation loss over the whole set by each constant (material.gradient of
+        material_sums()).  Default ``weights``: the case's layout over n, as the training step folds them."""
+        w = score_weights(weights, self._material_weights(self._n_collo), "(f_u, f_v, f_ut, f_vt, f_s11, f_s22, f_s12)")
+        return material.gradient(self.material_sums(), w, self.E, self.mu, self.rho, True)
+
     def callback(self, loss):                        # INF:278-280, SEMI:285-288
         self.count = self.count + 1
         self.loss_rec.append(loss)
@@ -254,7 +298,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin):
     # ------------------------------------------------------------------------------------------
     # training drivers
     # ------------------------------------------------------------------------------------------
-    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None, identify=None):
         """Adam loop of INF:282-319: contiguous collocation blocks, ``iter`` steps per block, all
         side sets fed whole to every block.  Returns the per-step lists
         (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss).  ``record="pre"`` (default): each recorded value is the loss
@@ -264,10 +308,17 @@ class DeepHPM(ShardedSetsModel, PredictMixin):
         ``every``-th step of this call (refine.RefineSchedule; the further entries are refine_collocation's keywords).
         ``validate``: None, or dict(every, points=(x, y, t), ref={name: column}, fields=(...)) -- the relative L2 of predict's fields against
         ``ref`` behind every ``every``-th step (validate.ValidateSchedule): the sums stay on the device until the block's host synchronisation,
-        the results are appended to ``self.val_rec`` as (step, dict)."""
+        the results are appended to ``self.val_rec`` as (step, dict).
+        ``identify``: None, or dict(params=("E", "mu"), lr=1e-3, every=1, bounds=dict(mu=(0.0, 0.49))) -- the named constants (any of E, mu,
+        rho) are identified while the net trains (material.MaterialSchedule): behind every ``every``-th step one forward-only call takes the
+        fp64 moment sums of the step's collocation block at the step's weights, and a float64 Adam on the host (log E, mu, log rho) moves the
+        constants; the next step's call sees them.  (step, E, mu, rho) is appended to ``self.material_rec``.  Cost: one more forward pass
+        over the block per identified step -- measured on an MI355X at 8x64, f16x3, 2 M points: 4.61 ms per step with None, 7.09 ms with
+        every=1, 5.24 ms with every=4 (profiles/material_sums_calls.txt); choose ``every`` accordingly.  With None the loop makes exactly the
+        calls it makes without the keyword."""
         if record not in ("pre", "post"):
             raise ValueError("record must be 'pre' or 'post'")
-        sched, vsched, step = schedule(self, refine), validate_schedule(self, validate), 0
+        sched, vsched, msched, step = schedule(self, refine), validate_schedule(self, validate), material.schedule(self, identify), 0
         loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss = [], [], [], [], []
         P = self.n_params
         col_num = self._n_collo
@@ -284,6 +335,9 @@ class DeepHPM(ShardedSetsModel, PredictMixin):
                 self._settle_adjoint_shift(self.engine, probe, P)
             for it in range(iter):
                 self.adam_t += 1
+                if msched is not None:
+                    # (the workspace holds the packed form of the current weights only behind a record="post" re-evaluation)
+                    msched.before_step(step + 1, idx_start, idx_end, packed=record == "post" and step > 0)
                 updated = self._loss_and_grad(idx_start, idx_end, sums_out=rec[it], adam=(learning_rate, self.adam_t))     # (sums_out: one launch less per step than copying afterwards)
                 if self._reduce:
                     rec[it].copy_(self._buf[P:])
@@ -295,8 +349,10 @@ class DeepHPM(ShardedSetsModel, PredictMixin):
                 if self.verbose and it % 10 == 0 and self.rank == 0:
                     tm = self._terms_from_sums(rec[it].detach().cpu().numpy().reshape(len(_SLOTS), 8), idx_end - idx_start)
                     print('It: %d, Loss: %.3e' % (it, tm["loss"]))
-                if sched is not None or vsched is not None:
+                if sched is not None or vsched is not None or msched is not None:
                     step += 1
+                    if msched is not None:
+                        msched.after_step()
                     if sched is not None:
                         sched.after_step(step)
                     if vsched is not None:
@@ -322,7 +378,8 @@ class DeepHPM(ShardedSetsModel, PredictMixin):
         parameter vector, loss and gradient from the device kernels; ``callback`` fires once per
         function evaluation like ScipyOptimizerInterface's loss_callback.  ``backend="torch"``: the same stage with the
         optimizer on the device as well (lbfgs_on_device), for when the host update is the bottleneck.  ``backend="hip"``: the library's own
-        L-BFGS (lbfgs_hip): no host round trip per evaluation, the callbacks arrive in batches.  Any other name raises ValueError."""
+        L-BFGS (lbfgs_hip): no host round trip per evaluation, the callbacks arrive in batches.  Any other name raises ValueError.
+        The material constants stay where they are: identification (train(identify=...)) belongs to the Adam loop only."""
         check_backend(backend)
         opts = dict(BFGS_OPTIONS[self.case])
         if options:
@@ -402,9 +459,9 @@ class DeepHPMConfined(DeepHPM):
             if layers is not None:
                 self._aux_nets[name] = self.load_NN(path, layers) if path else xavier_init(layers, np.random.default_rng(seed + off))
 
-    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None, identify=None):
         """CONF:373-408 returns three lists: (loss_f_uv, loss_f_s, loss)."""
-        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record, refine, validate)
+        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record, refine, validate, identify)
         return loss_f_uv, loss_f_s, loss
 
     def save_NN(self, fileDir, TYPE=''):

@@ -10,7 +10,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .capi import DEFAULT_LIB, FLAG_STATE_FP16, FLAG_TWO_KERNEL, FLAG_WEIGHTS_PACKED, PREC, PinnLib, PinnLibError, adjoint_shift
+from .capi import DEFAULT_LIB, FLAG_STATE_FP16, FLAG_TWO_KERNEL, FLAG_WEIGHTS_PACKED, MATERIAL_SUMS, PREC, PinnLib, PinnLibError, adjoint_shift
 
 
 def param_count(layers: Sequence[int]) -> int:
@@ -314,6 +314,21 @@ class HipEngine(LbfgsMixin):
         out = self._new_or_checked(out, (n,))
         self.lib.nc3d_residual_score(*self._net(params, (x, y, z, t), n, lb, ub, normalize), E, mu, rho, term_weights, out.data_ptr(),
                                      self._forward_mode(packed), *self._ws_tail())
+        return out
+
+    # ---- material identification: fp64 residual and moment sums over a point set ------------------------------------
+    def material_sums(self, params, x, y, t, lb, ub, normalize, E=2.5, mu=0.25, rho=1.0, plane_strain=True,
+                      out: Optional[torch.Tensor] = None, packed: bool = False):
+        """Returns the device float64 tensor [14] of pinn_wave2d_material_sums: the sums of squares of the seven wave residuals, then the
+        seven moment sums their derivatives by (c1, c2, G, rho) are made of (material.gradient turns them into dL/dE, dL/dmu, dL/drho).
+        Forward only, fixed summation order, no synchronisation."""
+        n = self._check(params, (x, y, t))
+        ws, ws_bytes = self._scratch("_material_ws", self.lib.material_sums_workspace_bytes)
+        if out is None:
+            out = torch.empty(MATERIAL_SUMS, dtype=torch.float64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == MATERIAL_SUMS
+        self.lib.wave2d_material_sums(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, out.data_ptr(),
+                                      self._forward_mode(packed), self._ws_ptr, self.ws_bytes, ws, ws_bytes, self._stream())
         return out
 
     # ---- predict heads: value + space tangents only, and the per-field error sums behind them ------------------------
