@@ -375,6 +375,43 @@ int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int
                                 const float term_weights[5], float* score_out,
                                 int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
+/* pinn_wave2d_material_sums for the plate family: what the collocation data say about E, mu and rho of the plane-stress plate.  The five
+ * residuals of PLATE:404-439 are linear in the Hooke coefficients (c1, c2, G) of PLATE:416-418 and in rho, so the derivative of a collocation
+ * loss by each is a moment sum of the composite's streams -- no reverse pass.
+ *   sums_out  DEVICE array of PINN_MATERIAL_SUMS_PLATE doubles:
+ *     k = 0..4 :  sum_n f_k(n)^2,  k in (f_u, f_v, f_s11, f_s22, f_s12)                    (what the loss call reports, here in fp64)
+ *     k = 5, 6 :  sum_n f_s11 * e11,  sum_n f_s11 * e22       e11 = dU/dx, e22 = dV/dy, e12 = dU/dy + dV/dx of the composite F = P + D*N
+ *     k = 7, 8 :  sum_n f_s22 * e11,  sum_n f_s22 * e22
+ *     k = 9    :  sum_n f_s12 * e12
+ *     k = 10,11:  sum_n f_u * d2U/dt2,  sum_n f_v * d2V/dt2
+ *   For a loss L = sum_i w_i sum_n f_i(n)^2 (w in the order of k = 0..4), with M_k = sums_out[k]:
+ *     dL/dc1  = -2 (w2 M5 + w3 M8)         dL/dc2  = -2 (w2 M6 + w3 M7)
+ *     dL/dG   = -2 w4 M9                   dL/drho = -2 (w0 M10 + w1 M11)
+ *   No weights enter the call; the chain rule from (c1, c2, G) to (E, mu) -- plane stress -- is the caller's.
+ * frozen_streams is the [2][5][5][n] array of pinn_plate2d_loss_grad at the same points.  Forward only: the composite and the residuals as
+ * pinn_plate2d_residual_score forms them (fp32); squares, products and every addition in fp64; the order of additions is fixed as in
+ * pinn_wave2d_material_sums (one record per wave, one workgroup adds the records in index order; PINN_PREC_FP32 adds its passes' totals in
+ * pass order), so the sums are a function of the arguments alone.  Split modes of every compiled width and PINN_PREC_FP32 (the other 16-bit
+ * modes: PINN_ERR_PRECISION, as the score call); pinn_min_workspace_bytes() is enough for any n; honours PINN_FLAG_WEIGHTS_PACKED;
+ * pinn_debug_path_counts does not count it.  No host synchronisation; n == 0 writes zeros (the point arrays and frozen_streams may be NULL).
+ * `sums_workspace`: pinn_material_sums_workspace_bytes() bytes of device scratch, 256-byte aligned -- the one size for all three calls.
+ * Errors: layers not 3 inputs -> 5 outputs: PINN_ERR_LAYERS; n < 0: PINN_ERR_SIZE; a NULL array that is needed: PINN_ERR_NULL; either
+ * workspace short or misaligned: PINN_ERR_WORKSPACE.
+ * Accuracy: the forward is the one of pinn_net_streams in the same mode; on top of it the head rounds at most 24 eps32 * sum_n a_i(n)^2
+ * (k < 5) or 24 eps32 * sum_n a_i(n) |g(n)| (k >= 5), a_i = the sum of the absolute values of the leaf terms of f_i (P, D*N, 2*D*N, with their
+ * coefficients), |g| the same of the second factor (measured: <= 0.06 of that bound in every family, 1 to 131 073 points).  Against the float64 sums, max_k |error_k| / S_k (S_k = bound_k / (24 eps32))
+ * over 1000 collocation points as a multiple of the same error of the sums evaluated in float32 on the host (MI355X): f16x3 1.78 / 0.50 / 0.98 at a fresh 4x32 net and the
+ * reference's trained 8x70 and 8x64 nets, PINN_PREC_FP32 1.85 / 0.52 / 0.43.
+ * Timing and the cost in training: profiles/material_family_calls.txt. */
+#define PINN_MATERIAL_SUMS_PLATE 12
+int pinn_plate2d_material_sums(const float* params_flat, const int* layers, int n_layers,
+                               const float* x, const float* y, const float* t, int64_t n,
+                               const double lb[3], const double ub[3], int normalize,
+                               const float* frozen_streams, double E, double mu, double rho,
+                               double* sums_out,
+                               int precision_mode, void* workspace, size_t ws_bytes,
+                               void* sums_workspace, size_t sums_ws_bytes, void* stream);
+
 /* The predict head of the plate family -- what predict evaluates (PLATE:561-570: the composite fields and strains of PLATE:358-388 on a point
  * set) in one launch of the uv net that carries the strain streams only: value, d/dx, d/dy (no time tangent, no second time derivative).
  *   frozen_streams  the [2][5][5][n] array of pinn_plate2d_loss_grad at the same points.  ONLY stream rows 0, 1, 2 (value, x, y) of D and of P
@@ -595,6 +632,39 @@ int pinn_nc3d_residual_score(const float* params_flat, const int* layers, int n_
                              const double lb[4], const double ub[4], int normalize,
                              double E, double mu, double rho, const float term_weights[12], float* score_out,
                              int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* pinn_wave2d_material_sums for the 3-D family: the twelve residuals of oracle/nc3d_oracle.py are linear in (c1, c2, G) = (lambda + 2G,
+ * lambda, G) -- the plane-strain coefficients of INF:238-241 -- and in rho.
+ *   sums_out  DEVICE array of PINN_MATERIAL_SUMS_NC3D doubles:
+ *     k = 0..11  :  sum_n f_k(n)^2 in the residual order above (f_u, f_v, f_w, f_ut, f_vt, f_wt, f_s11, f_s22, f_s33, f_s12, f_s13, f_s23)
+ *     k = 12, 13 :  sum_n f_s11 * e11,  sum_n f_s11 * (e22 + e33)         e11 = du/dx, e22 = dv/dy, e33 = dw/dz,
+ *     k = 14, 15 :  sum_n f_s22 * e22,  sum_n f_s22 * (e11 + e33)         e12 = du/dy + dv/dx, e13 = du/dz + dw/dx, e23 = dv/dz + dw/dy
+ *     k = 16, 17 :  sum_n f_s33 * e33,  sum_n f_s33 * (e11 + e22)
+ *     k = 18..20 :  sum_n f_s12 * e12,  sum_n f_s13 * e13,  sum_n f_s23 * e23
+ *     k = 21..23 :  sum_n f_u * d(ut)/dt,  sum_n f_v * d(vt)/dt,  sum_n f_w * d(wt)/dt
+ *   For a loss L = sum_i w_i sum_n f_i(n)^2 (w in the order of k = 0..11), with M_k = sums_out[k]:
+ *     dL/dc1  = -2 (w6 M12 + w7 M14 + w8 M16)        dL/dc2  = -2 (w6 M13 + w7 M15 + w8 M17)
+ *     dL/dG   = -2 (w9 M18 + w10 M19 + w11 M20)      dL/drho = -2 (w0 M21 + w1 M22 + w2 M23)
+ * Conventions of pinn_plate2d_material_sums: forward only, the residuals as pinn_nc3d_residual_score forms them (fp32; the pair sums
+ * e22 + e33 etc. one fp32 addition each), squares, products and every addition in fp64 in a fixed order; split modes of every compiled width
+ * and PINN_PREC_FP32 (which leaves the 24 terms of a pass in two halves of twelve rows -- squares, then moments -- and adds each sum's pass
+ * totals in pass order); pinn_min_workspace_bytes() is enough for any n; honours PINN_FLAG_WEIGHTS_PACKED; no path counter moves; no host
+ * synchronisation; n == 0 writes zeros (the point arrays may be NULL); `sums_workspace` of pinn_material_sums_workspace_bytes() bytes.
+ * Errors: layers not 4 inputs -> 12 outputs: PINN_ERR_LAYERS; n < 0: PINN_ERR_SIZE; a NULL array that is needed: PINN_ERR_NULL; either
+ * workspace short or misaligned: PINN_ERR_WORKSPACE; a non-split 16-bit mode: PINN_ERR_PRECISION.
+ * Accuracy: the forward is the one of pinn_nc3d_fields in the same mode; on top of it the head rounds at most 12 eps32 * sum_n a_i(n)^2
+ * (k < 12) or 12 eps32 * sum_n a_i(n) |g(n)| (k >= 12), a_i = the sum of the absolute values of the terms of f_i with their coefficients, |g|
+ * the same of the second factor (measured: <= 0.08 of that bound in every family, 1 to 131 073 points).  Against the float64 sums, max_k |error_k| / S_k over 1000 points as a multiple of the same error
+ * of the sums evaluated in float32 on the host (MI355X): f16x3 1.70 / 3.45 at a fresh 3x32 and a fresh 10x128 net, PINN_PREC_FP32 1.03 / 0.92.
+ * Timing and the cost in training: profiles/material_family_calls.txt. */
+#define PINN_MATERIAL_SUMS_NC3D 24
+int pinn_nc3d_material_sums(const float* params_flat, const int* layers, int n_layers,
+                            const float* x, const float* y, const float* z, const float* t, int64_t n,
+                            const double lb[4], const double ub[4], int normalize,
+                            double E, double mu, double rho,
+                            double* sums_out,
+                            int precision_mode, void* workspace, size_t ws_bytes,
+                            void* sums_workspace, size_t sums_ws_bytes, void* stream);
 
 /* Replaces tf.train.AdamOptimizer's update (INF:131-133; TF1 rule: epsilon outside the bias
  * correction).  step is 1-based.  All arrays are length n_params, updated in place. */

@@ -50,6 +50,8 @@ class StreamSet(C.Structure):
 
 MAX_BALLS = 4                      # PINN_MAX_BALLS
 MATERIAL_SUMS = 14                 # PINN_MATERIAL_SUMS
+MATERIAL_SUMS_PLATE = 12           # PINN_MATERIAL_SUMS_PLATE
+MATERIAL_SUMS_NC3D = 24            # PINN_MATERIAL_SUMS_NC3D
 KEYS_MODE = {"mask": 0, "sample": 1}             # PINN_KEYS_*
 
 
@@ -121,6 +123,7 @@ _MAT = [_f64, _f64, _f64]                          # E, mu, rho
 _WAVE = _MAT + [_i32, _pf32]                       # + plane_strain, term_weights[7]
 _OUT = [_vp, _vp, _i32]                            # loss_terms_out, grad_flat_out, accumulate
 _TAIL = [_i32, _vp, _sz, _vp]                      # precision_mode, workspace, ws_bytes, stream
+_SUMS = [_vp] + _TAIL[:3] + [_vp, _sz, _vp]        # sums_out, precision_mode, workspace, ws_bytes, sums_workspace, sums_ws_bytes, stream
 _ADAM = C.POINTER(AdamState)
 PROTOTYPES = {
     "pinn_supported_width": (_i32, [_i32]),
@@ -136,7 +139,7 @@ PROTOTYPES = {
     "pinn_wave2d_residual_score": (_i32, _NET + _PTS3 + _WAVE + [_vp] + _TAIL),
     "pinn_wave2d_predict": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
     "pinn_material_sums_workspace_bytes": (_sz, []),
-    "pinn_wave2d_material_sums": (_i32, _NET + _PTS3 + _MAT + [_i32, _vp] + _TAIL[:3] + [_vp, _sz, _vp]),
+    "pinn_wave2d_material_sums": (_i32, _NET + _PTS3 + _MAT + [_i32] + _SUMS),
     "pinn_field_error_workspace_bytes": (_sz, [_i64, _i32]),
     "pinn_field_error_sums": (_i32, [_vp, _i64, _pi32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "pinn_select_workspace_bytes": (_sz, [_i64]),
@@ -147,6 +150,7 @@ PROTOTYPES = {
     "pinn_net_streams": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
     "pinn_plate2d_loss_grad": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32] + _OUT + _TAIL),
     "pinn_plate2d_residual_score": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32, _vp] + _TAIL),
+    "pinn_plate2d_material_sums": (_i32, _NET + _PTS3 + [_vp] + _MAT + _SUMS),
     "pinn_plate2d_predict": (_i32, _NET + _PTS3 + [_vp, _vp] + _TAIL),
     "pinn_plate2d_traction_loss_grad": (_i32, _NET + _PTS3 + [_vp, _pf32] + _OUT + _TAIL),
     "pinn_stream_loss_grad": (_i32, _NET + _PTS3 + [_vp, _pf32] + _OUT + _TAIL),
@@ -161,6 +165,7 @@ PROTOTYPES = {
     "pinn_nc3d_data_loss_grad": (_i32, _NET + _PTS4 + [_vp, _pf32] + _OUT + _TAIL),
     "pinn_nc3d_fields": (_i32, _NET + _PTS4 + [_vp] + _TAIL),
     "pinn_nc3d_residual_score": (_i32, _NET + _PTS4 + _MAT + [_pf32, _vp] + _TAIL),
+    "pinn_nc3d_material_sums": (_i32, _NET + _PTS4 + _MAT + _SUMS),
     "pinn_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _i64, _vp]),
     "pinn_lbfgs_state_bytes": (_sz, [_i64, _i32]),
     "pinn_lbfgs_init": (_i32, [_vp, _sz, _i64, C.POINTER(LbfgsOptions), _pf32, _i32, _f64, _vp]),
@@ -486,6 +491,20 @@ class PinnLib:
                             stream=0):
         self.call("pinn_nc3d_residual_score", *self._net_points(params, layers, (x, y, z, t), n, lb, ub, normalize), float(E), float(mu), float(rho),
                   self._floats(term_weights, 12), score_out, *self._tail(prec, ws, ws_bytes, stream))
+
+    def plate2d_material_sums(self, params, layers, x, y, t, n, lb, ub, normalize, frozen, E, mu, rho, sums_out, prec, ws, ws_bytes, sums_ws,
+                              sums_ws_bytes, stream=0):
+        """pinn_plate2d_material_sums: sums_out (device, MATERIAL_SUMS_PLATE doubles) = the five sums of squared plate residuals, then the
+        seven moment sums of include/pinn_hip.h; frozen [2][5][5][n]; sums_ws: material_sums_workspace_bytes() of scratch"""
+        self.call("pinn_plate2d_material_sums", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), frozen, float(E), float(mu),
+                  float(rho), sums_out, *self._tail(prec, ws, ws_bytes, stream)[:3], sums_ws, int(sums_ws_bytes), stream)
+
+    def nc3d_material_sums(self, params, layers, x, y, z, t, n, lb, ub, normalize, E, mu, rho, sums_out, prec, ws, ws_bytes, sums_ws,
+                           sums_ws_bytes, stream=0):
+        """pinn_nc3d_material_sums: sums_out (device, MATERIAL_SUMS_NC3D doubles) = the twelve sums of squared 3-D residuals, then the twelve
+        moment sums of include/pinn_hip.h"""
+        self.call("pinn_nc3d_material_sums", *self._net_points(params, layers, (x, y, z, t), n, lb, ub, normalize), float(E), float(mu),
+                  float(rho), sums_out, *self._tail(prec, ws, ws_bytes, stream)[:3], sums_ws, int(sums_ws_bytes), stream)
 
     def plate2d_traction_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, aux, weights, loss_out, grad_out, accumulate,
                                    prec, ws, ws_bytes, stream=0):

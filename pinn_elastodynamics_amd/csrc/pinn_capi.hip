@@ -347,7 +347,8 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
     a.head = head;
     a.din = din;
     a.second = (din == 3 && ns == 5) ? 1 : 0;
-    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head) || head_is_predict(head) || head == HEAD_MATERIAL;
+    a.part = 0;
+    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head) || head_is_predict(head) || head_is_material(head);
     int pass = 0;
     for (long p0 = 0; p0 < c.n; p0 += mmax, ++pass) {
         a.p0 = p0;
@@ -358,14 +359,30 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
         a.fsq = a.Z + tensor;
         int blocks = (int)((a.m + 255) / 256);
         if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(fp32_chain_kernel, dim3(blocks), dim3(256), 0, st, a);
+        // (the plate and 3-D material heads live in an instantiation of their own, so that the other calls' kernel does not move)
+        void (*const chain)(const Fp32Args) = (head == HEAD_MATERIAL_PLATE || head == HEAD_MATERIAL3D) ? fp32_chain_kernel<true> : fp32_chain_kernel<false>;
+        hipLaunchKernelGGL(chain, dim3(blocks), dim3(256), 0, st, a);
         if (!forward_only) {
             hipLaunchKernelGGL(fp32_sum_kernel, dim3(nterms), dim3(256), 0, st, (const float*)a.fsq, a.m, c.loss_out, pass > 0 ? 1 : 0);
             hipLaunchKernelGGL(fp32_wgrad_kernel, dim3((c.net.nparams + 255) / 256), dim3(256), 0, st, a, c.grad_out, (c.accumulate || pass > 0) ? 1 : 0);
         }
         int rc = (int)hipGetLastError();
-        // pinn_wave2d_material_sums: the pass's 14 term rows added in fp64, its total into the sums in pass order
-        if (!rc && head == HEAD_MATERIAL) rc = material::launch_fp32_pass(a.fsq, a.m, c.moment_part, c.moment_out, pass, st);
+        // the material sums: the pass's term rows added in fp64, its total into the sums in pass order
+        if (!rc && head == HEAD_MATERIAL) rc = material::launch_fp32_pass<MATERIAL_SUMS>(a.fsq, a.m, c.moment_part, c.moment_out, pass, st);
+        if (!rc && head == HEAD_MATERIAL_PLATE) rc = material::launch_fp32_pass<MATERIAL_SUMS_PLATE>(a.fsq, a.m, c.moment_part, c.moment_out, pass, st);
+        if (!rc && head == HEAD_MATERIAL3D) {
+            // 24 terms in FP32_TERMS = 16 rows: the squares' half (left by the launch above) into sums 0..11, then the pass once more for
+            // the moments' half into sums 12..23 -- every sum still takes its passes' totals in pass order
+            static_assert(MATERIAL_SUMS_3D == 2 * MATERIAL_SUMS_PLATE && FP32_TERMS >= MATERIAL_SUMS_PLATE, "two halves of twelve rows");
+            rc = material::launch_fp32_pass<MATERIAL_SUMS_PLATE>(a.fsq, a.m, c.moment_part, c.moment_out, pass, st);
+            if (!rc) {
+                a.part = 1;
+                hipLaunchKernelGGL(chain, dim3(blocks), dim3(256), 0, st, a);
+                a.part = 0;
+                rc = (int)hipGetLastError();
+            }
+            if (!rc) rc = material::launch_fp32_pass<MATERIAL_SUMS_PLATE>(a.fsq, a.m, c.moment_part, c.moment_out + MATERIAL_SUMS_PLATE, pass, st);
+        }
         if (rc) return rc;
     }
     return PINN_OK;
@@ -652,6 +669,51 @@ int pinn_wave2d_material_sums(const float* params_flat, const int* layers, int n
     static_assert(FP32_TERMS >= MATERIAL_SUMS, "term rows of a PINN_PREC_FP32 pass");
     if (!impl) return fp32_call(c, HEAD_MATERIAL, 0, 4, 3, false);
     return impl->wave_material(c);
+}
+
+// the sums workspace of the plate and 3-D material calls: checked against the one sizing function, then handed to the call
+static int material_args(Call& c, double* sums_out, void* sums_workspace, size_t sums_ws_bytes) {
+    if (((uintptr_t)sums_workspace & 255) != 0 || sums_ws_bytes < pinn_material_sums_workspace_bytes()) return PINN_ERR_WORKSPACE;
+    c.moment_part = static_cast<double*>(sums_workspace);
+    c.moment_out = sums_out;
+    return PINN_OK;
+}
+
+int pinn_plate2d_material_sums(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
+                               int64_t n, const double lb[3], const double ub[3], int normalize, const float* frozen_streams, double E,
+                               double mu, double rho, double* sums_out, int precision_mode, void* workspace, size_t ws_bytes,
+                               void* sums_workspace, size_t sums_ws_bytes, void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (!sums_out || !sums_workspace || (n > 0 && !frozen_streams)) return PINN_ERR_NULL;
+    if (c.net.nout != 5) return PINN_ERR_LAYERS;
+    if ((rc = material_args(c, sums_out, sums_workspace, sums_ws_bytes))) return rc;
+    set_hooke(c, E, mu, rho, 0);
+    c.aux = frozen_streams;
+    static_assert(PINN_MATERIAL_SUMS_PLATE == MATERIAL_SUMS_PLATE, "sums of the header and of the head");
+    if (c.n == 0) return (int)hipMemsetAsync(sums_out, 0, PINN_MATERIAL_SUMS_PLATE * sizeof(double), c.stream);
+    if (!impl) return fp32_call(c, HEAD_MATERIAL_PLATE, 0, 5, 3, false);
+    return impl->plate_material(c);
+}
+
+int pinn_nc3d_material_sums(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
+                            const float* t, int64_t n, const double lb[4], const double ub[4], int normalize, double E, double mu, double rho,
+                            double* sums_out, int precision_mode, void* workspace, size_t ws_bytes, void* sums_workspace, size_t sums_ws_bytes,
+                            void* stream) {
+    Call c;
+    const Impl* impl = nullptr;
+    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
+    if (rc) return rc;
+    if (!sums_out || !sums_workspace) return PINN_ERR_NULL;
+    if (c.net.nout != 12) return PINN_ERR_LAYERS;
+    if ((rc = material_args(c, sums_out, sums_workspace, sums_ws_bytes))) return rc;
+    set_hooke(c, E, mu, rho, 1);
+    static_assert(PINN_MATERIAL_SUMS_NC3D == MATERIAL_SUMS_3D, "sums of the header and of the head");
+    if (c.n == 0) return (int)hipMemsetAsync(sums_out, 0, PINN_MATERIAL_SUMS_NC3D * sizeof(double), c.stream);
+    if (!impl) return fp32_call(c, HEAD_MATERIAL3D, 0, 5, 4, false);
+    return impl->nc3d_material(c);
 }
 
 size_t pinn_field_error_workspace_bytes(int64_t n, int n_rows) {

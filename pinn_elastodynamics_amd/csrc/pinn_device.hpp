@@ -254,11 +254,25 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 //               squares and the seven moment sums the derivatives of the collocation loss by (c1, c2, G, rho) are made of, the residuals being
 //               linear in those four (pinn_wave2d_material_sums).  One record of MATERIAL_SUMS doubles per wave through `moment_part`; a second
 //               launch (pinn_material.hpp) adds the records in index order.  No weights, no per-point output.
+// HEAD_MATERIAL_PLATE: the same for the plate family, 5 streams, `aux` = frozen streams: the composite and the five plane-stress residuals as
+//               HEAD_SCORE_PLATE forms them, reduced to MATERIAL_SUMS_PLATE fp64 sums -- five squares, seven moments
+//               (pinn_plate2d_material_sums)
+// HEAD_MATERIAL3D: the same for the 4-input family, 5 first-order streams, 12 outputs: the twelve residuals of HEAD_SCORE3D reduced to
+//               MATERIAL_SUMS_3D fp64 sums -- twelve squares, twelve moments (pinn_nc3d_material_sums)
 enum { HEAD_WAVE = 0, HEAD_DATA = 1, HEAD_FIELDS = 2, HEAD_PLATE = 3, HEAD_TRACTION = 4, HEAD_STREAMS = 5, HEAD_NC3D = 6, HEAD_DATA3D = 7,
-       HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11, HEAD_PREDICT = 12, HEAD_PREDICT_PLATE = 13, HEAD_MATERIAL = 14 };
-constexpr int MATERIAL_SUMS = 14;     // HEAD_MATERIAL: sums per record (PINN_MATERIAL_SUMS)
+       HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11, HEAD_PREDICT = 12, HEAD_PREDICT_PLATE = 13, HEAD_MATERIAL = 14,
+       HEAD_MATERIAL_PLATE = 15, HEAD_MATERIAL3D = 16 };
+constexpr int MATERIAL_SUMS = 14;           // HEAD_MATERIAL: sums per record (PINN_MATERIAL_SUMS)
+constexpr int MATERIAL_SUMS_PLATE = 12;     // HEAD_MATERIAL_PLATE (PINN_MATERIAL_SUMS_PLATE)
+constexpr int MATERIAL_SUMS_3D = 24;        // HEAD_MATERIAL3D (PINN_MATERIAL_SUMS_NC3D)
+constexpr int MATERIAL_SUMS_MAX = 24;       // the longest record: what the sums workspace is sized for
 __host__ __device__ constexpr bool head_is_3d(int head) {
-    return head == HEAD_NC3D || head == HEAD_DATA3D || head == HEAD_FIELDS3D || head == HEAD_SCORE3D;
+    return head == HEAD_NC3D || head == HEAD_DATA3D || head == HEAD_FIELDS3D || head == HEAD_SCORE3D || head == HEAD_MATERIAL3D;
+}
+__host__ __device__ constexpr bool head_is_material(int head) { return head == HEAD_MATERIAL || head == HEAD_MATERIAL_PLATE || head == HEAD_MATERIAL3D; }
+// sums per record of a material head (1 for every other head: the size of an array that is never used)
+__host__ __device__ constexpr int material_sums_of(int head) {
+    return head == HEAD_MATERIAL ? MATERIAL_SUMS : head == HEAD_MATERIAL_PLATE ? MATERIAL_SUMS_PLATE : head == HEAD_MATERIAL3D ? MATERIAL_SUMS_3D : 1;
 }
 __host__ __device__ constexpr bool head_is_score(int head) { return head == HEAD_SCORE || head == HEAD_SCORE_PLATE || head == HEAD_SCORE3D; }
 __host__ __device__ constexpr bool head_is_predict(int head) { return head == HEAD_PREDICT || head == HEAD_PREDICT_PLATE; }
@@ -284,9 +298,9 @@ struct ChainArgs {
     long Z_tile_stride;
     float* loss_part;          // [total waves][8 or LOSS_SLOTS_3D] per-wave partial sums of squares
     float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  score heads: [n];  predict heads: [8][n]
-    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_PREDICT_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
+    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_PREDICT_PLATE / HEAD_MATERIAL_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
     float w5[5][8];            // HEAD_STREAMS: per (stream, output) weights, max-normalised
-    double* moment_part;       // HEAD_MATERIAL: [total waves][MATERIAL_SUMS] per-wave sums
+    double* moment_part;       // material heads: [total waves][material_sums_of(HEAD)] per-wave sums
 };
 
 struct WgradArgs {
@@ -723,15 +737,15 @@ struct Chain {
         const int wpb = blockDim.x >> 6;
         const long gwave = (long)blockIdx.x * wpb + (threadIdx.x >> 6), nwaves = (long)gridDim.x * wpb;
         const int nl = a.net.nl;
-        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD) || head_is_predict(HEAD) || HEAD == HEAD_MATERIAL;
+        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD) || head_is_predict(HEAD) || head_is_material(HEAD);
         constexpr bool SPILL = !FWD_ONLY;
         __shared__ __attribute__((aligned(16))) char spill_lds[4 * 1024];      // one 1 KB transpose record per wave (256-thread blocks)
         char* rec = spill_lds + (threadIdx.x >> 6) * 1024;
         float lsum[LT];
 #pragma unroll
         for (int i = 0; i < LT; ++i) lsum[i] = 0.0f;
-        constexpr int MS = HEAD == HEAD_MATERIAL ? MATERIAL_SUMS : 1;
-        double msum[MS];      // HEAD_MATERIAL: the lane's sums over every tile of the wave (q == 0 lanes hold a point)
+        constexpr int MS = material_sums_of(HEAD);
+        double msum[MS];      // material heads: the lane's sums over every tile of the wave (q == 0 lanes hold a point)
 #pragma unroll
         for (int k = 0; k < MS; ++k) msum[k] = 0.0;
 
@@ -1087,6 +1101,93 @@ struct Chain {
                         msum[12] += fd[0] * (double)T[2];
                         msum[13] += fd[1] * (double)T[3];
                     }
+                } else if constexpr (HEAD == HEAD_MATERIAL_PLATE) {
+                    // the plate's sums: composite F = P + D*N and the five residuals exactly as HEAD_SCORE_PLATE forms them (PLATE:383-387,
+                    // 404-439), a third copy, in fp32; squares and products with the composite's strains / accelerations in fp64 per lane.
+                    // A padded lane adds nothing.
+                    float D[5][5], F[5][5];
+#pragma unroll
+                    for (int st = 0; st < 5; ++st)
+#pragma unroll
+                        for (int o = 0; o < 5; ++o) {
+                            D[st][o] = a.aux[((long)(0 * 5 + st) * 5 + o) * a.n + pidx[nb]];
+                            F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + pidx[nb]];      // start from P
+                        }
+#pragma unroll
+                    for (int o = 0; o < 5; ++o) {
+                        const float n0 = Y[0][nb][o];
+                        F[0][o] += D[0][o] * n0;
+#pragma unroll
+                        for (int k = 1; k <= 3; ++k) F[k][o] += D[k][o] * n0 + D[0][o] * Y[k][nb][o];
+                        F[4][o] += D[4][o] * n0 + 2.0f * D[3][o] * Y[3][nb][o] + D[0][o] * Y[4][nb][o];
+                    }
+                    const float e11 = F[1][0], e22 = F[2][1], e12 = F[2][0] + F[1][1];
+                    float f[5];
+                    f[0] = F[1][2] + F[2][4] - a.rho * F[4][0];                       // f_u   PLATE:436
+                    f[1] = F[2][3] + F[1][4] - a.rho * F[4][1];                       // f_v   PLATE:437
+                    f[2] = F[0][2] - (a.c1 * e11 + a.c2 * e22);                       // f_s11 PLATE:421
+                    f[3] = F[0][3] - (a.c2 * e11 + a.c1 * e22);                       // f_s22 PLATE:423
+                    f[4] = F[0][4] - a.G * e12;                                       // f_s12 PLATE:422
+                    if (q == 0 && valid[nb]) {
+                        double fd[5];
+#pragma unroll
+                        for (int i = 0; i < 5; ++i) {
+                            fd[i] = (double)f[i];
+                            msum[i] += fd[i] * fd[i];
+                        }
+                        const double d11 = (double)e11, d22 = (double)e22;
+                        msum[5] += fd[2] * d11;
+                        msum[6] += fd[2] * d22;
+                        msum[7] += fd[3] * d11;
+                        msum[8] += fd[3] * d22;
+                        msum[9] += fd[4] * (double)e12;
+                        msum[10] += fd[0] * (double)F[4][0];
+                        msum[11] += fd[1] * (double)F[4][1];
+                    }
+                } else if constexpr (HEAD == HEAD_MATERIAL3D) {
+                    // the 3-D sums: the twelve residuals of HEAD_SCORE3D (oracle/nc3d_oracle.py), a third copy, in fp32; the pair sums of the
+                    // normal strains are single fp32 additions, widened for the product only.  A padded lane adds nothing.
+                    const float(&V)[16] = Y[0][nb];
+                    const float(&X)[16] = Y[1][nb];
+                    const float(&Yy)[16] = Y[2][nb];
+                    const float(&Zz)[16] = Y[3][nb];
+                    const float(&T)[16] = Y[4][nb];
+                    const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
+                    const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
+                    const float p23 = e22 + e33, p13 = e11 + e33, p12 = e11 + e22;
+                    float f[12];
+                    f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
+                    f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
+                    f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
+                    f[3] = T[0] - V[3];
+                    f[4] = T[1] - V[4];
+                    f[5] = T[2] - V[5];
+                    f[6] = V[6] - (a.c1 * e11 + a.c2 * p23);
+                    f[7] = V[7] - (a.c1 * e22 + a.c2 * p13);
+                    f[8] = V[8] - (a.c1 * e33 + a.c2 * p12);
+                    f[9] = V[9] - a.G * e12;
+                    f[10] = V[10] - a.G * e13;
+                    f[11] = V[11] - a.G * e23;
+                    if (q == 0 && valid[nb]) {
+                        double fd[12];
+#pragma unroll
+                        for (int i = 0; i < 12; ++i) {
+                            fd[i] = (double)f[i];
+                            msum[i] += fd[i] * fd[i];
+                        }
+                        msum[12] += fd[6] * (double)e11;
+                        msum[13] += fd[6] * (double)p23;
+                        msum[14] += fd[7] * (double)e22;
+                        msum[15] += fd[7] * (double)p13;
+                        msum[16] += fd[8] * (double)e33;
+                        msum[17] += fd[8] * (double)p12;
+                        msum[18] += fd[9] * (double)e12;
+                        msum[19] += fd[10] * (double)e13;
+                        msum[20] += fd[11] * (double)e23;
+                        msum[21] += fd[0] * (double)T[3];
+                        msum[22] += fd[1] * (double)T[4];
+                        msum[23] += fd[2] * (double)T[5];
+                    }
                 } else if constexpr (HEAD == HEAD_SCORE_PLATE) {
                     // the plate's score: composite F = P + D*N and the five residuals exactly as HEAD_PLATE forms them (PLATE:383-387,
                     // 404-439), a second copy like HEAD_SCORE's; outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt)
@@ -1254,16 +1355,16 @@ struct Chain {
                 if (lane == 0) a.loss_part[gwave * LT + i] = v;
             }
         }
-        if constexpr (HEAD == HEAD_MATERIAL) {
+        if constexpr (head_is_material(HEAD)) {
             // the wave's record: a fixed tree over the 16 point lanes (q == 0), written by lane 0; a wave without tiles writes zeros
 #pragma unroll
-            for (int k = 0; k < MATERIAL_SUMS; ++k) {
+            for (int k = 0; k < MS; ++k) {
                 double v = msum[k];
                 v += __shfl_xor(v, 1);
                 v += __shfl_xor(v, 2);
                 v += __shfl_xor(v, 4);
                 v += __shfl_xor(v, 8);
-                if (lane == 0) a.moment_part[gwave * MATERIAL_SUMS + k] = v;
+                if (lane == 0) a.moment_part[gwave * MS + k] = v;
             }
         }
     }

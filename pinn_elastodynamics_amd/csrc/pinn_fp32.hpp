@@ -35,7 +35,7 @@ struct Fp32Args {
     float w5[5][8];            // HEAD_STREAMS: weight per (stream, output)
     float w5n[5][8];           // ... divided by the largest: the loss sums of that head are reported weight-normalised
     const float* targets;      // data heads: [nout][n] or nullptr
-    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE: frozen streams [2][5][5][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or nullptr
+    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_MATERIAL_PLATE: frozen streams [2][5][5][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or nullptr
     float* S;                  // [nl+1][ns][hr][m]: S_0 = inputs and tangent seeds (first din rows), S_l = state behind hidden layer l
     float* Z;                  // [nl+1][ns][hr][m]: Z_l = adjoint of the pre-activations of weight layer l (Z_nl: nout rows)
     float* fsq;                // [FP32_TERMS][m]: squared residuals of the pass
@@ -45,10 +45,14 @@ struct Fp32Args {
     int head;                  // HEAD_*
     int din;                   // 3 or 4
     int second;                // stream 4 carries the second time derivative (din = 3, ns = 5)
+    int part;                  // HEAD_MATERIAL3D: which twelve of its 24 terms this launch leaves in `fsq` (0: the squares, 1: the moments)
 };
 
 __device__ __forceinline__ long fp32_idx(const Fp32Args& a, int l, int s, int f, long p) { return (((long)l * a.ns + s) * a.hr + f) * a.m + p; }
 
+// FAMILY_SUMS: with the heads of pinn_plate2d_material_sums and pinn_nc3d_material_sums compiled in.  Every other call launches the
+// instantiation without them: its code and registers are those of the kernel before these heads existed.
+template <bool FAMILY_SUMS>
 __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
     const int nl = a.net.nl, H = a.net.h, NO = a.net.nout, ns = a.ns, din = a.din;
     const int nt = a.second ? 3 : ns - 1;      // first-order tangent streams 1..nt (stream s differentiates by input s - 1; din = 3: the last input is t)
@@ -177,6 +181,80 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             a.fsq[11L * a.m + p] = f[6] * e12;
             a.fsq[12L * a.m + p] = f[0] * Y[3][2];
             a.fsq[13L * a.m + p] = f[1] * Y[3][3];
+            continue;
+        }
+        if (FAMILY_SUMS && a.head == HEAD_MATERIAL_PLATE) {
+            // pinn_plate2d_material_sums: the composite and the five residuals of HEAD_PLATE below, their squares and their products with the
+            // composite's strains / accelerations, one fp32 row each of `fsq`
+            float D[5][5], F[5][5];
+            for (int st = 0; st < 5; ++st)
+                for (int o = 0; o < 5; ++o) {
+                    D[st][o] = a.aux[((long)(0 * 5 + st) * 5 + o) * a.n + gp];
+                    F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + gp];
+                }
+            for (int o = 0; o < 5; ++o) {
+                const float n0 = Y[0][o];
+                F[0][o] += D[0][o] * n0;
+                for (int k = 1; k <= 3; ++k) F[k][o] += D[k][o] * n0 + D[0][o] * Y[k][o];
+                F[4][o] += D[4][o] * n0 + 2.0f * D[3][o] * Y[3][o] + D[0][o] * Y[4][o];
+            }
+            const float e11 = F[1][0], e22 = F[2][1], e12 = F[2][0] + F[1][1];
+            float f[5];
+            f[0] = F[1][2] + F[2][4] - a.rho * F[4][0];
+            f[1] = F[2][3] + F[1][4] - a.rho * F[4][1];
+            f[2] = F[0][2] - (a.c1 * e11 + a.c2 * e22);
+            f[3] = F[0][3] - (a.c2 * e11 + a.c1 * e22);
+            f[4] = F[0][4] - a.G * e12;
+            for (int i = 0; i < 5; ++i) a.fsq[(long)i * a.m + p] = f[i] * f[i];
+            a.fsq[5L * a.m + p] = f[2] * e11;
+            a.fsq[6L * a.m + p] = f[2] * e22;
+            a.fsq[7L * a.m + p] = f[3] * e11;
+            a.fsq[8L * a.m + p] = f[3] * e22;
+            a.fsq[9L * a.m + p] = f[4] * e12;
+            a.fsq[10L * a.m + p] = f[0] * F[4][0];
+            a.fsq[11L * a.m + p] = f[1] * F[4][1];
+            continue;
+        }
+        if (FAMILY_SUMS && a.head == HEAD_MATERIAL3D) {
+            // pinn_nc3d_material_sums: the twelve residuals of HEAD_NC3D below; this launch leaves the twelve squares (part 0) or the twelve
+            // moments (part 1) in rows 0..11 of `fsq` -- FP32_TERMS rows do not hold all 24
+            const float* V = Y[0];
+            const float* X = Y[1];
+            const float* Yy = Y[2];
+            const float* Zz = Y[3];
+            const float* T = Y[4];
+            const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
+            const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
+            const float p23 = e22 + e33, p13 = e11 + e33, p12 = e11 + e22;
+            float f[12];
+            f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
+            f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
+            f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
+            f[3] = T[0] - V[3];
+            f[4] = T[1] - V[4];
+            f[5] = T[2] - V[5];
+            f[6] = V[6] - (a.c1 * e11 + a.c2 * p23);
+            f[7] = V[7] - (a.c1 * e22 + a.c2 * p13);
+            f[8] = V[8] - (a.c1 * e33 + a.c2 * p12);
+            f[9] = V[9] - a.G * e12;
+            f[10] = V[10] - a.G * e13;
+            f[11] = V[11] - a.G * e23;
+            if (a.part == 0) {
+                for (int i = 0; i < 12; ++i) a.fsq[(long)i * a.m + p] = f[i] * f[i];
+            } else {
+                a.fsq[0L * a.m + p] = f[6] * e11;
+                a.fsq[1L * a.m + p] = f[6] * p23;
+                a.fsq[2L * a.m + p] = f[7] * e22;
+                a.fsq[3L * a.m + p] = f[7] * p13;
+                a.fsq[4L * a.m + p] = f[8] * e33;
+                a.fsq[5L * a.m + p] = f[8] * p12;
+                a.fsq[6L * a.m + p] = f[9] * e12;
+                a.fsq[7L * a.m + p] = f[10] * e13;
+                a.fsq[8L * a.m + p] = f[11] * e23;
+                a.fsq[9L * a.m + p] = f[0] * T[3];
+                a.fsq[10L * a.m + p] = f[1] * T[4];
+                a.fsq[11L * a.m + p] = f[2] * T[5];
+            }
             continue;
         }
         if (a.head == HEAD_SCORE_PLATE) {

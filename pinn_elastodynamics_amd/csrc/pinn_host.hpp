@@ -80,7 +80,7 @@ struct Call {
     DataSet sets[4];
     // fields head
     float* fields_out;
-    // material head (pinn_wave2d_material_sums): per-wave records, MATERIAL_SUMS doubles each, and the 14 sums
+    // material heads (pinn_*_material_sums): per-wave records, material_sums_of(head) doubles each, and the sums
     double* moment_part = nullptr;
     double* moment_out = nullptr;
     // plate / traction / stream-target heads
@@ -136,6 +136,9 @@ struct Impl {
     int (*plate_predict)(const Call&);
     // the fp64 residual and moment sums of the wave family (forward only, HEAD_MATERIAL + the one-workgroup final pass)
     int (*wave_material)(const Call&);
+    // the same for the plate family (HEAD_MATERIAL_PLATE, `aux` = frozen streams) and the 4-input family (HEAD_MATERIAL3D); split modes only
+    int (*plate_material)(const Call&);
+    int (*nc3d_material)(const Call&);
     // pinn_debug_cache_policy: the collocation kernel compiled for this net and head (asked of the F16 split-3 line of the net's width)
     int (*cache_policy)(const NetDesc&, int head, size_t* images_bytes, size_t* sums_bytes);
 };
@@ -866,8 +869,21 @@ struct Host {
         if (rc) return rc;
         const int nrecords = chain_blocks(forward_tiles<nb<4>()>(c.n)) * 4;
         static_assert(MAX_BLOCKS * 4 <= material::MAX_RECORDS, "records of the largest chain grid");
-        return material::launch_final(c.moment_part, nrecords, c.moment_out, 0, c.stream);
+        return material::launch_final<MATERIAL_SUMS>(c.moment_part, nrecords, c.moment_out, 0, c.stream);
     }
+    // pinn_plate2d_material_sums / pinn_nc3d_material_sums: five streams; split-precision variants only, like their score calls
+    template <int HEAD>
+    static int family_material(const Call& c) {
+        if constexpr (SPLIT == 3) {
+            const int rc = forward<5, HEAD>(c, false);
+            if (rc) return rc;
+            const int nrecords = chain_blocks(forward_tiles<nb<5>()>(c.n)) * 4;
+            return material::launch_final<material_sums_of(HEAD)>(c.moment_part, nrecords, c.moment_out, 0, c.stream);
+        }
+        return PINN_ERR_PRECISION;
+    }
+    static int plate_material(const Call& c) { return family_material<HEAD_MATERIAL_PLATE>(c); }
+    static int nc3d_material(const Call& c) { return family_material<HEAD_MATERIAL3D>(c); }
 
     // 5-stream family (plate): split-precision variants only
     static int plate_loss_grad(const Call& c) {
@@ -1004,7 +1020,7 @@ struct Host {
         static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
                                &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
                                &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score,
-                               &wave_predict, &plate_predict, &wave_material, &cache_policy};
+                               &wave_predict, &plate_predict, &wave_material, &plate_material, &nc3d_material, &cache_policy};
         return &I;
     }
 };

@@ -45,7 +45,7 @@ BFGS_OPTIONS = {
 _SLOTS = ("collo", "IC", "SRC", "NB", "FIX")   # 8 floats each in the loss-sum buffer
 
 
-class DeepHPM(ShardedSetsModel, PredictMixin):
+class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
     """Drop-in for the reference's model class on the wave cases (INF:21-376)."""
     N_IN, COLLO_NAMES = 3, ("x_c", "y_c", "t_c")
     COLLO_TERMS, SUMS_STRIDE, SLOTS = (4, 3), 8, _SLOTS
@@ -176,41 +176,15 @@ class DeepHPM(ShardedSetsModel, PredictMixin):
         """what _loss_and_grad puts on the seven collocation terms of a block of ``n_blk`` points"""
         return [self.layout["f_uv"] / n_blk] * 4 + [self.layout["f_s"] / n_blk] * 3
 
-    def _material_sums_device(self, lo, hi, packed=False):
-        """the 14 sums of engine.material_sums over the rows [lo, hi) of the collocation set as a float64 tensor on the engine's device: this
-        rank's rows, then summed over the process group by torch.distributed.all_reduce (whatever ``collective`` is: the P2P kernel is for the
-        gradient buffer).  No host synchronisation."""
+    def _material_rows(self):
+        return self._n_collo
+
+    def _material_engine_sums(self, lo, hi, **kw):
         s, e = self._shard(lo, hi)
-        if e > s:
-            x, y, t = self._rows(lo, hi)
-            kw = {"packed": True} if packed else {}
-            sums = self.engine.material_sums(self.theta, x, y, t, self.lb, self.ub, self.normalize, self.E, self.mu, self.rho, True, **kw)
-        else:
-            sums = torch.zeros(material.N_SUMS, dtype=torch.float64, device=self.device)
-        if self._reduce:
-            torch.distributed.all_reduce(sums, group=self.pg)
-        return sums
-
-    def _material_sums_async(self, lo, hi, packed=False):
-        """_material_sums_device on its way to the host: returns fetch() -> numpy [14], which waits for nothing enqueued after this call"""
-        if self.device.type == "cuda" and not hasattr(self, "_material_pinned"):
-            self._material_pinned = material.pinned_sums()
-        return material.sums_to_host(self._material_sums_device(lo, hi, packed), getattr(self, "_material_pinned", None))
-
-    def material_sums(self, idx_start=0, idx_end=None):
-        """The 14 sums of pinn_wave2d_material_sums (include/pinn_hip.h) over the rows [idx_start, idx_end) of the collocation set -- default:
-        the whole set -- at the current weights and constants, host numpy [14]: the seven sums of squared residuals of net_f_sig, then the seven
-        moment sums.  Data parallel: every rank computes its shard's rows and gets the total."""
-        hi = self._n_collo if idx_end is None else int(idx_end)
-        out = self._material_sums_async(int(idx_start), hi)()
-        self._check_collective()
-        return out
-
-    def material_gradient(self, weights=None):
-        """dict(E, mu, rho) -> the derivative of the collocation loss over the whole set by each constant (material.gradient of
-        material_sums()).  Default ``weights``: the case's layout over n, as the training step folds them."""
-        w = score_weights(weights, self._material_weights(self._n_collo), "(f_u, f_v, f_ut, f_vt, f_s11, f_s22, f_s12)")
-        return material.gradient(self.material_sums(), w, self.E, self.mu, self.rho, True)
+        if e <= s:
+            return None
+        x, y, t = self._rows(lo, hi)
+        return self.engine.material_sums(self.theta, x, y, t, self.lb, self.ub, self.normalize, self.E, self.mu, self.rho, True, **kw)
 
     def callback(self, loss):                        # INF:278-280, SEMI:285-288
         self.count = self.count + 1

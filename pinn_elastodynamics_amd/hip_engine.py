@@ -10,7 +10,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .capi import DEFAULT_LIB, FLAG_STATE_FP16, FLAG_TWO_KERNEL, FLAG_WEIGHTS_PACKED, MATERIAL_SUMS, PREC, PinnLib, PinnLibError, adjoint_shift
+from .capi import DEFAULT_LIB, FLAG_STATE_FP16, FLAG_TWO_KERNEL, FLAG_WEIGHTS_PACKED, MATERIAL_SUMS, MATERIAL_SUMS_NC3D, MATERIAL_SUMS_PLATE, PREC, PinnLib, PinnLibError, adjoint_shift
 
 
 def param_count(layers: Sequence[int]) -> int:
@@ -329,6 +329,35 @@ class HipEngine(LbfgsMixin):
         assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == MATERIAL_SUMS
         self.lib.wave2d_material_sums(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, out.data_ptr(),
                                       self._forward_mode(packed), self._ws_ptr, self.ws_bytes, ws, ws_bytes, self._stream())
+        return out
+
+    def _sums_out(self, out, n_sums):
+        """the float64 device tensor [n_sums] a material call writes: ``out`` checked, or a new one"""
+        if out is None:
+            out = torch.empty(n_sums, dtype=torch.float64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n_sums
+        return out
+
+    def plate_material_sums(self, params, x, y, t, lb, ub, normalize, frozen, E, mu, rho, out: Optional[torch.Tensor] = None, packed: bool = False):
+        """The same for the plate family (pinn_plate2d_material_sums): ``frozen`` is the [2, 5, 5, n] tensor of plate_loss_grad at these points.
+        Returns the device float64 tensor [12]: the sums of squares of the five plane-stress residuals, then the seven moment sums
+        (material.gradient with material.PLATE)."""
+        n = self._check(params, (x, y, t))
+        self._chk(frozen, 50 * n)
+        ws, ws_bytes = self._scratch("_material_ws", self.lib.material_sums_workspace_bytes)
+        out = self._sums_out(out, MATERIAL_SUMS_PLATE)
+        self.lib.plate2d_material_sums(*self._net(params, (x, y, t), n, lb, ub, normalize), frozen.data_ptr(), E, mu, rho, out.data_ptr(),
+                                       self._forward_mode(packed), self._ws_ptr, self.ws_bytes, ws, ws_bytes, self._stream())
+        return out
+
+    def nc3d_material_sums(self, params, x, y, z, t, lb, ub, normalize, E, mu, rho, out: Optional[torch.Tensor] = None, packed: bool = False):
+        """The same for the 4-input family (pinn_nc3d_material_sums).  Returns the device float64 tensor [24]: the sums of squares of the twelve
+        residuals of nc3d_loss_grad, then the twelve moment sums (material.gradient with material.NC3D)."""
+        n = self._check(params, (x, y, z, t))
+        ws, ws_bytes = self._scratch("_material_ws", self.lib.material_sums_workspace_bytes)
+        out = self._sums_out(out, MATERIAL_SUMS_NC3D)
+        self.lib.nc3d_material_sums(*self._net(params, (x, y, z, t), n, lb, ub, normalize), E, mu, rho, out.data_ptr(),
+                                    self._forward_mode(packed), self._ws_ptr, self.ws_bytes, ws, ws_bytes, self._stream())
         return out
 
     # ---- predict heads: value + space tangents only, and the per-field error sums behind them ------------------------

@@ -17,6 +17,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import material
 from .model_base import ShardedSetsModel
 from .optim import all_reduce_sum, check_backend
 from .refine import Candidates, refine_sharded_set, schedule, score_weights
@@ -26,7 +27,7 @@ _SLOTS = ("collo", "IC", "SRC", "NB")          # 16 floats each in the loss-sum 
 LOSS_LAYOUT_3D = dict(f_uv=5.0, f_s=5.0, IC=2.0, SRC=2.0, NB=2.0)        # the semi-infinite script's weights (SEMI:127)
 
 
-class NavierCauchy3D(ShardedSetsModel):
+class NavierCauchy3D(ShardedSetsModel, material.MaterialMixin):
     """NavierCauchy3D(Collo[N,4], SRC[Ns,7], IC[Ni,4], TOP[Nt,4], uv_layers, lb[4], ub[4], ExistModel=0, modelDir='')
 
     Collo: collocation points (x, y, z, t); SRC: points with prescribed displacement (x, y, z, t, u, v, w) -- the source;
@@ -34,6 +35,7 @@ class NavierCauchy3D(ShardedSetsModel):
     uv_layers = [4] + depth * [width] + [12]."""
     N_IN, COLLO_NAMES = 4, ("x_c", "y_c", "z_c", "t_c")
     COLLO_TERMS, SUMS_STRIDE, SLOTS = (6, 6), 16, _SLOTS
+    material_family = material.NC3D
 
     def __init__(self, Collo, SRC, IC, TOP, uv_layers, lb, ub, ExistModel=0, modelDir='', *, precision="f16x3", engine=None, seed=1111,
                  process_group=None, verbose=True, E=2.5, mu=0.25, rho=1.0, normalize=True, layout: Optional[dict] = None,
@@ -133,6 +135,21 @@ class NavierCauchy3D(ShardedSetsModel):
         C = Candidates(self, candidates, 4, "(x, y, z, t)", select, power, c, seed, stream, box, exclude)
         return refine_sharded_set(self, C, n_replace, self._score_weights(weights), ("x_c", "y_c", "z_c", "t_c"))
 
+    # ---- identification of E, mu, rho: the moment sums of the collocation residuals (material.py) ----------------------
+    def _material_weights(self, n_blk):
+        """what _loss_and_grad puts on the twelve collocation terms of a block of ``n_blk`` points"""
+        return [self.layout["f_uv"] / n_blk] * 6 + [self.layout["f_s"] / n_blk] * 6
+
+    def _material_rows(self):
+        return self._n_collo
+
+    def _material_engine_sums(self, lo, hi, **kw):
+        s, e = self._shard(lo, hi)
+        if e <= s:
+            return None
+        x, y, z, t = self._rows(lo, hi)
+        return self.engine.nc3d_material_sums(self.theta, x, y, z, t, self.lb, self.ub, self.normalize, self.E, self.mu, self.rho, **kw)
+
     def callback(self, loss):
         self.count += 1
         self.loss_rec.append(loss)
@@ -173,12 +190,17 @@ class NavierCauchy3D(ShardedSetsModel):
             all_reduce_sum(buf, self.pg, getattr(self, "collective_events", None), getattr(self, "_p2p", None))
 
     # ---- training drivers ---------------------------------------------------------------------------------------------
-    def train(self, iter, learning_rate, batch_num, refine=None):
+    def train(self, iter, learning_rate, batch_num, refine=None, identify=None):
         """Adam loop with the reference's block-sequential batching (SEMI:290-328): returns the per-step lists
         (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss) -- the loss each step's gradient was taken at.  ``refine``: None, or
-        dict(every, candidates, n_replace, ...): refine_collocation with device-drawn candidates behind every ``every``-th step of this call."""
+        dict(every, candidates, n_replace, ...): refine_collocation with device-drawn candidates behind every ``every``-th step of this call.
+        ``identify``: None, or dict(params=("E", "mu"), lr=1e-3, every=1, bounds=...) as in elastic_wave.DeepHPM.train: behind every
+        ``every``-th step one forward-only call takes the 24 fp64 sums of the step's block (pinn_nc3d_material_sums) at the step's weights
+        and constants, a float64 Adam on the host moves the named constants, (step, E, mu, rho) is appended to ``self.material_rec``.  Cost,
+        MI355X, 10x128, f16x3, 200 000 points: 4.85 ms per step with None, 5.97 with every=1, 5.10 with every=4
+        (profiles/material_family_calls.txt).  With None the loop makes exactly the calls it makes without the keyword."""
         P, L = self.n_params, len(_SLOTS)
-        sched, step = schedule(self, refine), 0
+        sched, msched, step = schedule(self, refine), material.schedule(self, identify), 0
         hist = ([], [], [], [], [])
         for i in range(batch_num):
             lo, hi = int(i * self._n_collo / batch_num), int((i + 1) * self._n_collo / batch_num)
@@ -191,13 +213,18 @@ class NavierCauchy3D(ShardedSetsModel):
             if iter > 0:
                 self._settle_adjoint_shift(self.engine, probe, P)
             for it in range(iter):
+                if msched is not None:
+                    msched.before_step(step + 1, lo, hi)
                 self._loss_and_grad(lo, hi)
                 rec[it].copy_(self._buf[P:])
                 self.adam_t += 1
                 self.engine.adam_step(self.theta, self.adam_m, self.adam_v, self._buf[:P], learning_rate, self.adam_t)
-                if sched is not None:
+                if sched is not None or msched is not None:
                     step += 1
-                    sched.after_step(step)
+                    if msched is not None:
+                        msched.after_step()
+                    if sched is not None:
+                        sched.after_step(step)
             sums = rec.detach().cpu().numpy().reshape(iter, L, 16)
             self._check_collective()                 # (behind the block's one host synchronisation)
             if iter > 0 and not bool(torch.isfinite(self.theta).all()):
@@ -211,7 +238,8 @@ class NavierCauchy3D(ShardedSetsModel):
     def train_bfgs(self, batch_num, options: Optional[dict] = None, backend: str = "scipy"):
         """L-BFGS stage on the device kernels, as SEMI:330-344.  ``backend="scipy"`` (default): scipy's L-BFGS-B on the host over a float64
         copy of the flat vector; ``"torch"``: torch.optim.LBFGS on the device (optim.lbfgs_on_device); ``"hip"``: the library's own
-        L-BFGS, no host round trip per evaluation (optim.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError."""
+        L-BFGS, no host round trip per evaluation (optim.lbfgs_hip: the callbacks arrive in batches).  Any other name raises ValueError.
+        The material constants stay where they are: identification (train(identify=...)) belongs to the Adam loop only."""
         check_backend(backend)
         L = len(_SLOTS)
         opts = dict(maxiter=1000, maxfun=1000, maxcor=50, maxls=50, ftol=0.001 * float(np.finfo(float).eps))       # SEMI:130-137

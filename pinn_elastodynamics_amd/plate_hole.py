@@ -18,6 +18,7 @@ import torch
 
 from .model_base import ModelBase
 from .optim import all_reduce_sum, check_backend, device_array, lbfgs_hip, lbfgs_on_device, pack_params
+from . import material
 from .refine import Candidates, empty_result, schedule, score_weights, select_pairs, update_host_columns
 from .validate import PredictMixin, schedule as validate_schedule
 
@@ -29,7 +30,9 @@ BFGS_OPTIONS = {   # PLATE:220-247
 }
 
 
-class PINN(ModelBase, PredictMixin):
+class PINN(ModelBase, PredictMixin, material.MaterialMixin):
+    material_family = material.PLATE
+
     def __init__(self, Collo, HOLE, IC, LF, RT, UP, LW, DIST, uv_layers, dist_layers, part_layers, lb, ub,
                  partDir='', distDir='', uvDir='', *, precision="f16x3", engines=None, seed=1111, process_group=None, verbose=True,
                  always_reduce=False, collective="rccl", p2p_timeout_s=None):
@@ -264,6 +267,23 @@ class PINN(ModelBase, PredictMixin):
             out["candidates"] = pts
         return out
 
+    # ---- identification of E, mu, rho: the moment sums of the collocation residuals (material.py) ----------------------
+    def _material_weights(self, n_blk):
+        """what _loss_and_grad puts on the five collocation terms: 10 / n_collo each (the set is never split into blocks)"""
+        return [10.0 / n_blk] * 5
+
+    def _material_rows(self):
+        return self.n_collo
+
+    def _material_engine_sums(self, lo, hi, **kw):
+        if (lo, hi) != (0, self.n_collo):
+            raise ValueError("the plate trains on its whole collocation set: material sums are taken over all of it")
+        x, y, t = self._collo
+        if x.numel() == 0:
+            return None
+        return self.eng["uv"].plate_material_sums(self.theta["uv"], x, y, t, self.lb, self.ub, False, self._frozen_collo, self.E, self.mu,
+                                                  self.rho, **kw)
+
     def callback(self, loss):
         self.count = self.count + 1
         if self.verbose and self.rank == 0:
@@ -313,14 +333,20 @@ class PINN(ModelBase, PredictMixin):
         out["loss"] = 10.0 * (out["loss_f_uv"] + out["loss_f_s"] + out["loss_HOLE"])
         return out
 
-    def train(self, iter, learning_rate, refine=None, validate=None):
+    def train(self, iter, learning_rate, refine=None, validate=None, identify=None):
         """Adam loop of PLATE:475-506 (whole collocation set every step).  Returns (loss_f_uv, loss_f_s, loss_HOLE, loss) lists;
         as in elastic_wave.DeepHPM.train the recorded values are those the step's gradient was taken at.  ``refine``: None, or
         dict(every, candidates, n_replace, ...): refine_collocation with device-drawn candidates behind every ``every``-th step of this call.
         ``validate``: None, or dict(every, points=(x, y, t), ref={name: column}, fields=(...)): the relative L2 of predict's fields against ``ref``
-        behind every ``every``-th step, downloaded at the loop's host synchronisation into ``self.val_rec`` as (step, dict)."""
+        behind every ``every``-th step, downloaded at the loop's host synchronisation into ``self.val_rec`` as (step, dict).
+        ``identify``: None, or dict(params=("E", "mu"), lr=1e-3, every=1, bounds=...) as in elastic_wave.DeepHPM.train: behind every
+        ``every``-th step one forward-only call takes the 12 fp64 sums of the collocation set (pinn_plate2d_material_sums, with the frozen
+        streams the step uses) at the step's weights and constants, a float64 Adam on the host moves the named constants -- plane stress --,
+        (step, E, mu, rho) is appended to ``self.material_rec``.  Cost, MI355X, 8x64, f16x3, 500 000 points: 1.57 ms per step with None, 2.35 with
+        every=1, 1.78 with every=4 (profiles/material_family_calls.txt).  With None the loop makes exactly
+        the calls it makes without the keyword.  The train_bfgs* stages leave the constants alone."""
         P = self.theta["uv"].numel()
-        sched, vsched = schedule(self, refine), validate_schedule(self, validate)
+        sched, vsched, msched = schedule(self, refine), validate_schedule(self, validate), material.schedule(self, identify)
         rec = torch.empty((iter, 16), dtype=torch.float32, device=self.device)
 
         def probe():
@@ -331,12 +357,16 @@ class PINN(ModelBase, PredictMixin):
             self._settle_adjoint_shift(self.eng["uv"], probe, P)      # (E = 20 makes the plate's early residuals large)
         for it in range(iter):
             self.adam_t += 1
+            if msched is not None:
+                msched.before_step(it + 1, 0, self.n_collo)
             updated = self._loss_and_grad(adam=(learning_rate, self.adam_t))
             rec[it].copy_(self._buf[P:])
             if not updated:
                 self.eng["uv"].adam_step(self.theta["uv"], self.adam_m, self.adam_v, self._buf[:P], learning_rate, self.adam_t)
             if self.verbose and it % 10 == 0 and self.rank == 0:
                 print('It: %d, Loss: %.6e' % (it, self._terms(rec[it].detach().cpu().numpy())["loss"]))
+            if msched is not None:
+                msched.after_step()
             if sched is not None:
                 sched.after_step(it + 1)
             if vsched is not None:
