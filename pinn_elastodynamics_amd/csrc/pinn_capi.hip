@@ -116,7 +116,7 @@ bool xcd_tail_device_ok() {
 
 extern "C" {
 
-int pinn_abi_version(void) { return 2; }      // 2 (round 6): PINN_IPC_HANDLE_BYTES 64 -> 128, pinn_p2p_set_timeout_ms / _peek_status, pinn_wave2d_step_checked
+int pinn_abi_version(void) { return 2; }      // 2 (round 6): PINN_IPC_HANDLE_BYTES 64 -> 128, pinn_p2p_set_timeout_ms / _peek_status, pinn_wave2d_loss_grad_checked
 
 float pinn_fused_weight_limit(void) { return FUSED_OPERAND_MAX / FUSED_WEIGHT_SCALE; }
 
@@ -224,6 +224,8 @@ static int empty_batch(const Call& c, int nterms) {
     return rc;
 }
 
+// What every entry point is given, checked and decoded into a default-constructed Call: the flags of the precision word, the net, the points,
+// the input map, the workspace and the stream; impl = the kernel family of (mode, width).
 static int prepare(const float* params, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
                    const double* lb, const double* ub, int normalize, int precision_mode, void* ws, size_t ws_bytes, void* stream,
                    Call& c, const Impl*& impl, int din = 3, const float* z = nullptr) {
@@ -244,31 +246,19 @@ static int prepare(const float* params, const int* layers, int n_layers, const f
     impl = precision_mode == PINN_PREC_FP32 ? nullptr : find_impl(precision_mode, width);
     if (!impl && precision_mode != PINN_PREC_FP32) return PINN_ERR_LAYERS;
     c.params = params;
-    c.z = z;
-    c.nsets = 0;
-    c.targets = nullptr;
     c.x = x;
     c.y = y;
+    c.z = z;
     c.t = t;
     c.n = (long)n;
     input_map(lb, ub, normalize, c, din);
     c.ws = ws;
     c.ws_bytes = ws_bytes;
     c.stream = (hipStream_t)stream;
-    c.loss_out = nullptr;
-    c.grad_out = nullptr;
-    c.accumulate = 0;
-    c.c1 = c.c2 = c.G = c.rho = 0.0f;
-    for (int i = 0; i < 16; ++i) c.tw[i] = 0.0f;
-    c.targets = nullptr;
-    c.fields_out = nullptr;
-    c.aux = nullptr;
-    for (int i = 0; i < 5; ++i)
-        for (int o = 0; o < 8; ++o) c.w5[i][o] = 0.0f;
+    // the process-wide debug hooks
     c.prof_ms = g_prof_ms;
     c.ring = g_ring.armed ? &g_ring : nullptr;
     c.use_fused = two_kernel ? 0 : g_use_fused;
-    c.one_stream_head = 0;
     c.dbg_stamps = g_dbg_stamps;
     return PINN_OK;
 }
@@ -313,12 +303,13 @@ size_t pinn_min_workspace_bytes(const int* layers, int n_layers, int precision_m
 }
 
 // PINN_PREC_FP32: plain fp32 arithmetic (pinn_fp32.hpp), the points walked in as many passes as the workspace holds.
-// ns = streams of the head (1: data / traction heads, 4: wave / fields, 5: plate family and the 4-input heads), din = inputs.
-static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, bool counted = true) {
+// Head, streams, inputs and terms are those of the call's row of CALLS.
+static int fp32_call(const Call& c, const CallRow& r) {
+    const int head = r.head, ns = r.ns, din = r.din, nterms = r.nterms ? r.nterms : c.net.nout;
     hipStream_t st = c.stream;
     const size_t per_point = fp32_bytes_per_point(c.net, ns);
     if (((uintptr_t)c.ws & 255) != 0 || c.ws_bytes < per_point * 256) return PINN_ERR_WORKSPACE;
-    if (counted) ++g_path_counts[PINN_PATH_FP32];      // (the residual score is no loss + gradient call: not counted)
+    if (r.counted) ++g_path_counts[PINN_PATH_FP32];      // (the residual score is no loss + gradient call: not counted)
     long mmax = (long)(c.ws_bytes / per_point);
     if (mmax > (1L << 20)) mmax = 1L << 20;
     Fp32Args a;
@@ -348,7 +339,7 @@ static int fp32_call(const Call& c, int head, int nterms, int ns, int din = 3, b
     a.din = din;
     a.second = (din == 3 && ns == 5) ? 1 : 0;
     a.part = 0;
-    const bool forward_only = head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head) || head_is_predict(head) || head_is_material(head);
+    const bool forward_only = head_is_forward_only(head);
     int pass = 0;
     for (long p0 = 0; p0 < c.n; p0 += mmax, ++pass) {
         a.p0 = p0;
@@ -443,25 +434,6 @@ static int zero_empty_sets(const pinn_point_set* sets, int n_sets, int nout, hip
     return PINN_OK;
 }
 
-// ---- the common end of the single-set entry points, behind prepare() and the entry's own checks: the outputs, the empty batch, then
-// PINN_PREC_FP32 (impl == NULL: fp32_call with the head's streams `ns`) or the kernel family's call
-static int run_loss_grad(Call& c, const Impl* impl, float* loss_out, float* grad_out, int accumulate, int nterms, int (*Impl::*call)(const Call&),
-                         int head, int ns, int din = 3) {
-    c.loss_out = loss_out;
-    c.grad_out = grad_out;
-    c.accumulate = accumulate;
-    if (c.n == 0) return empty_batch(c, nterms);
-    if (!impl) return fp32_call(c, head, nterms, ns, din);
-    return (impl->*call)(c);
-}
-// (forward only: fields, streams, the residual scores and the predict heads -- the last two are not counted as a path)
-static int run_forward(Call& c, const Impl* impl, float* out, int (*Impl::*call)(const Call&), int head, int ns, int din = 3) {
-    c.fields_out = out;
-    if (c.n == 0) return PINN_OK;
-    if (!impl) return fp32_call(c, head, 0, ns, din, !head_is_score(head) && !head_is_predict(head));
-    return (impl->*call)(c);
-}
-
 // Hooke coefficients: plane strain INF:238-241 -- also the isotropic 3-D law, c1 = lambda + 2G, c2 = lambda (oracle/nc3d_oracle.py) --, plane
 // stress PLATE:416-418.  Evaluated in double, each cast to float once.
 static void set_hooke(Call& c, double E, double mu, double rho, int plane_strain) {
@@ -480,28 +452,90 @@ static void set_hooke(Call& c, double E, double mu, double rho, int plane_strain
     c.rho = (float)rho;
 }
 
-static int wave2d_loss_grad_impl(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
-                          int64_t n, const double lb[3], const double ub[3], int normalize, double E, double mu, double rho,
-                          int plane_strain, const float term_weights[7], float* loss_terms_out, float* grad_flat_out, int accumulate,
-                          int precision_mode, void* workspace, size_t ws_bytes, void* stream, float* prof_ms) {
+size_t pinn_material_sums_workspace_bytes(void) { return align_up(material::ws_bytes(), 256); }
+static_assert(PINN_MATERIAL_SUMS == MATERIAL_SUMS && PINN_MATERIAL_SUMS_PLATE == MATERIAL_SUMS_PLATE && PINN_MATERIAL_SUMS_NC3D == MATERIAL_SUMS_3D,
+              "sums of the header and of the heads");
+static_assert(FP32_TERMS >= MATERIAL_SUMS, "term rows of a PINN_PREC_FP32 pass");
+
+// the sums workspace of the material calls: checked against the one sizing function, then handed to the call
+static int material_args(Call& c, double* sums_out, void* sums_workspace, size_t sums_ws_bytes) {
+    if (((uintptr_t)sums_workspace & 255) != 0 || sums_ws_bytes < pinn_material_sums_workspace_bytes()) return PINN_ERR_WORKSPACE;
+    c.moment_part = static_cast<double*>(sums_workspace);
+    c.moment_out = sums_out;
+    return PINN_OK;
+}
+
+// ---- The single-set per-point entry points.  What all of them are given goes to prepare(); Own holds what an entry point takes besides:
+// the pointers its call requires are named by the call's row of CALLS (weights, aux) and by its shape (the outputs).
+struct Own {
+    bool has_material = false;             // material constants (the heads with a residual)
+    double E = 0.0, mu = 0.0, rho = 0.0;
+    int plane_strain = 0;
+    const float* weights = nullptr;        // term weights[row.nterms], output weights[n_out], or the stream-target weights[5][n_out]
+    const float* aux = nullptr;            // -> Call::aux: frozen streams, frozen streams + normals; the stream targets (optional)
+    const float* targets = nullptr;        // -> Call::targets (optional: NULL = zeros)
+    float* loss_out = nullptr;             // loss + gradient calls
+    float* grad_out = nullptr;
+    int accumulate = 0;
+    float* out = nullptr;                  // forward calls: the per-point output
+    double* sums_out = nullptr;            // forward + final sum calls
+    void* sums_ws = nullptr;
+    size_t sums_ws_bytes = 0;
+    float* prof_ms = nullptr;              // pinn_wave2d_loss_grad_profile
+    void material(double E_, double mu_, double rho_, int plane_strain_) { has_material = true; E = E_; mu = mu_; rho = rho_; plane_strain = plane_strain_; }
+    void loss_grad(float* loss, float* grad, int acc) { loss_out = loss; grad_out = grad; accumulate = acc; }
+    void sums(double* out_, void* ws, size_t ws_bytes) { sums_out = out_; sums_ws = ws; sums_ws_bytes = ws_bytes; }
+};
+
+// The order of the checks is the contract tests/test_capi_errors.py holds: prepare() (a NULL params / workspace before a negative n, then the
+// points, the box, the precision word and the layer list), the entry's own pointers, the output count, the sums workspace.
+static int point_call(int id, const float* params, const int* layers, int n_layers, const float* x, const float* y, const float* z, const float* t,
+                      int64_t n, const double* lb, const double* ub, int normalize, int precision_mode, void* ws, size_t ws_bytes, void* stream,
+                      const Own& o) {
+    const CallRow& r = CALLS[id];
     Call c;
     const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    int rc = prepare(params, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, ws, ws_bytes, stream, c, impl, r.din, z);
     if (rc) return rc;
-    if (!term_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
-    if (c.net.nout != 7) return PINN_ERR_LAYERS;
-    set_hooke(c, E, mu, rho, plane_strain);
-    for (int i = 0; i < 7; ++i) c.tw[i] = term_weights[i];
-    if (prof_ms) c.prof_ms = prof_ms;
-    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 7, &Impl::wave_loss_grad, HEAD_WAVE, 4);
+    if ((r.with_tw && !o.weights) || (r.needs_aux && n > 0 && !o.aux)) return PINN_ERR_NULL;
+    if (r.shape == SHAPE_LOSS_GRAD ? (!o.loss_out || !o.grad_out) : r.shape == SHAPE_FORWARD_SUMS ? (!o.sums_out || !o.sums_ws) : (n > 0 && !o.out))
+        return PINN_ERR_NULL;
+    if (r.nout && c.net.nout != r.nout) return PINN_ERR_LAYERS;
+    if (r.shape == SHAPE_FORWARD_SUMS && (rc = material_args(c, o.sums_out, o.sums_ws, o.sums_ws_bytes))) return rc;
+    if (o.has_material) set_hooke(c, o.E, o.mu, o.rho, o.plane_strain);
+    const int nterms = r.nterms ? r.nterms : c.net.nout;
+    if (r.head == HEAD_STREAMS) {
+        for (int s = 0; s < 5; ++s)
+            for (int k = 0; k < c.net.nout; ++k) c.w5[s][k] = o.weights[s * c.net.nout + k];
+    } else if (r.with_tw) {
+        for (int i = 0; i < nterms; ++i) c.tw[i] = o.weights[i];
+    }
+    c.aux = o.aux;
+    c.targets = o.targets;
+    c.loss_out = o.loss_out;
+    c.grad_out = o.grad_out;
+    c.accumulate = o.accumulate;
+    c.fields_out = o.out;
+    if (o.prof_ms) c.prof_ms = o.prof_ms;
+    // An empty point set contributes nothing (see empty_batch): zero sums, no per-point output
+    if (c.n == 0) {
+        if (r.shape == SHAPE_LOSS_GRAD) return empty_batch(c, nterms);
+        if (r.shape == SHAPE_FORWARD_SUMS) return (int)hipMemsetAsync(o.sums_out, 0, material_sums_of(r.head) * sizeof(double), c.stream);
+        return PINN_OK;
+    }
+    // PINN_PREC_FP32 (impl == NULL), or the kernel family's run of this call
+    return impl ? impl->run[id](c) : fp32_call(c, r);
 }
 
 int pinn_wave2d_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                           int64_t n, const double lb[3], const double ub[3], int normalize, double E, double mu, double rho,
                           int plane_strain, const float term_weights[7], float* loss_terms_out, float* grad_flat_out, int accumulate,
                           int precision_mode, void* workspace, size_t ws_bytes, void* stream) {
-    return wave2d_loss_grad_impl(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights,
-                                 loss_terms_out, grad_flat_out, accumulate, precision_mode, workspace, ws_bytes, stream, nullptr);
+    Own o;
+    o.material(E, mu, rho, plane_strain);
+    o.weights = term_weights;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_WAVE_LOSS_GRAD, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_wave2d_loss_grad_profile(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
@@ -509,22 +543,23 @@ int pinn_wave2d_loss_grad_profile(const float* params_flat, const int* layers, i
                                   int plane_strain, const float term_weights[7], float* loss_terms_out, float* grad_flat_out,
                                   int accumulate, int precision_mode, void* workspace, size_t ws_bytes, void* stream, float kernel_ms[4]) {
     if (!kernel_ms) return PINN_ERR_NULL;
-    return wave2d_loss_grad_impl(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights,
-                                 loss_terms_out, grad_flat_out, accumulate, precision_mode, workspace, ws_bytes, stream, kernel_ms);
+    Own o;
+    o.material(E, mu, rho, plane_strain);
+    o.weights = term_weights;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    o.prof_ms = kernel_ms;
+    return point_call(CALL_WAVE_LOSS_GRAD, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_data_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                         int64_t n, const double lb[3], const double ub[3], int normalize, const float* targets,
                         const float* out_weights, float* loss_terms_out, float* grad_flat_out, int accumulate, int precision_mode,
                         void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (!out_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
-    for (int i = 0; i < c.net.nout; ++i) c.tw[i] = out_weights[i];
-    c.targets = targets;
-    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, c.net.nout, &Impl::data_loss_grad, HEAD_DATA, 1);
+    Own o;
+    o.weights = out_weights;
+    o.targets = targets;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_DATA_LOSS_GRAD, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_data_loss_grad_multi(const float* params_flat, const int* layers, int n_layers, const pinn_point_set* sets, int n_sets,
@@ -554,12 +589,12 @@ int pinn_data_loss_grad_multi(const float* params_flat, const int* layers, int n
         if (!accumulate) return (int)hipMemsetAsync(grad_flat_out, 0, (size_t)c.net.nparams * sizeof(float), st);
         return 0;
     }
-    if (impl) return impl->data_loss_grad(c);
+    if (impl) return impl->run[CALL_DATA_LOSS_GRAD](c);
     // PINN_PREC_FP32: one set after the other into the same gradient
     bool first_set = true;
     for (int k = 0; k < n_sets; ++k) {
         if (sets[k].n <= 0) continue;
-        if ((rc = fp32_call(set_call(c, c.sets[k], first_set), HEAD_DATA, c.net.nout, 1))) return rc;
+        if ((rc = fp32_call(set_call(c, c.sets[k], first_set), CALLS[CALL_DATA_LOSS_GRAD]))) return rc;
         first_set = false;
     }
     return PINN_OK;
@@ -613,107 +648,59 @@ int pinn_wave2d_step(float* params_flat, const int* layers, int n_layers, const 
 int pinn_wave2d_fields(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                        int64_t n, const double lb[3], const double ub[3], int normalize, float* fields_out, int precision_mode,
                        void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (n > 0 && !fields_out) return PINN_ERR_NULL;
-    return run_forward(c, impl, fields_out, &Impl::fields, HEAD_FIELDS, 4);
+    Own o;
+    o.out = fields_out;
+    return point_call(CALL_WAVE_FIELDS, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_wave2d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                                int64_t n, const double lb[3], const double ub[3], int normalize, double E, double mu, double rho,
                                int plane_strain, const float term_weights[7], float* score_out, int precision_mode, void* workspace,
                                size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (!term_weights || (n > 0 && !score_out)) return PINN_ERR_NULL;
-    if (c.net.nout != 7) return PINN_ERR_LAYERS;
-    set_hooke(c, E, mu, rho, plane_strain);
-    for (int i = 0; i < 7; ++i) c.tw[i] = term_weights[i];
-    return run_forward(c, impl, score_out, &Impl::wave_score, HEAD_SCORE, 4);
+    Own o;
+    o.material(E, mu, rho, plane_strain);
+    o.weights = term_weights;
+    o.out = score_out;
+    return point_call(CALL_WAVE_SCORE, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_wave2d_predict(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
                         const double lb[3], const double ub[3], int normalize, float* out, int precision_mode, void* workspace, size_t ws_bytes,
                         void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (n > 0 && !out) return PINN_ERR_NULL;
-    if (c.net.nout != 7) return PINN_ERR_LAYERS;
-    return run_forward(c, impl, out, &Impl::wave_predict, HEAD_PREDICT, 3);
+    Own o;
+    o.out = out;
+    return point_call(CALL_WAVE_PREDICT, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
-
-size_t pinn_material_sums_workspace_bytes(void) { return align_up(material::ws_bytes(), 256); }
 
 int pinn_wave2d_material_sums(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                               int64_t n, const double lb[3], const double ub[3], int normalize, double E, double mu, double rho,
                               int plane_strain, double* sums_out, int precision_mode, void* workspace, size_t ws_bytes, void* sums_workspace,
                               size_t sums_ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (!sums_out || !sums_workspace) return PINN_ERR_NULL;
-    if (c.net.nout != 7) return PINN_ERR_LAYERS;
-    if (((uintptr_t)sums_workspace & 255) != 0 || sums_ws_bytes < pinn_material_sums_workspace_bytes()) return PINN_ERR_WORKSPACE;
-    set_hooke(c, E, mu, rho, plane_strain);
-    c.moment_part = static_cast<double*>(sums_workspace);
-    c.moment_out = sums_out;
-    if (c.n == 0) return (int)hipMemsetAsync(sums_out, 0, PINN_MATERIAL_SUMS * sizeof(double), c.stream);      // an empty set: zero sums
-    static_assert(PINN_MATERIAL_SUMS == MATERIAL_SUMS, "sums of the header and of the head");
-    static_assert(FP32_TERMS >= MATERIAL_SUMS, "term rows of a PINN_PREC_FP32 pass");
-    if (!impl) return fp32_call(c, HEAD_MATERIAL, 0, 4, 3, false);
-    return impl->wave_material(c);
-}
-
-// the sums workspace of the plate and 3-D material calls: checked against the one sizing function, then handed to the call
-static int material_args(Call& c, double* sums_out, void* sums_workspace, size_t sums_ws_bytes) {
-    if (((uintptr_t)sums_workspace & 255) != 0 || sums_ws_bytes < pinn_material_sums_workspace_bytes()) return PINN_ERR_WORKSPACE;
-    c.moment_part = static_cast<double*>(sums_workspace);
-    c.moment_out = sums_out;
-    return PINN_OK;
+    Own o;
+    o.material(E, mu, rho, plane_strain);
+    o.sums(sums_out, sums_workspace, sums_ws_bytes);
+    return point_call(CALL_WAVE_MATERIAL, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_plate2d_material_sums(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                                int64_t n, const double lb[3], const double ub[3], int normalize, const float* frozen_streams, double E,
                                double mu, double rho, double* sums_out, int precision_mode, void* workspace, size_t ws_bytes,
                                void* sums_workspace, size_t sums_ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (!sums_out || !sums_workspace || (n > 0 && !frozen_streams)) return PINN_ERR_NULL;
-    if (c.net.nout != 5) return PINN_ERR_LAYERS;
-    if ((rc = material_args(c, sums_out, sums_workspace, sums_ws_bytes))) return rc;
-    set_hooke(c, E, mu, rho, 0);
-    c.aux = frozen_streams;
-    static_assert(PINN_MATERIAL_SUMS_PLATE == MATERIAL_SUMS_PLATE, "sums of the header and of the head");
-    if (c.n == 0) return (int)hipMemsetAsync(sums_out, 0, PINN_MATERIAL_SUMS_PLATE * sizeof(double), c.stream);
-    if (!impl) return fp32_call(c, HEAD_MATERIAL_PLATE, 0, 5, 3, false);
-    return impl->plate_material(c);
+    Own o;
+    o.material(E, mu, rho, 0);
+    o.aux = frozen_streams;
+    o.sums(sums_out, sums_workspace, sums_ws_bytes);
+    return point_call(CALL_PLATE_MATERIAL, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_nc3d_material_sums(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
                             const float* t, int64_t n, const double lb[4], const double ub[4], int normalize, double E, double mu, double rho,
                             double* sums_out, int precision_mode, void* workspace, size_t ws_bytes, void* sums_workspace, size_t sums_ws_bytes,
                             void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
-    if (rc) return rc;
-    if (!sums_out || !sums_workspace) return PINN_ERR_NULL;
-    if (c.net.nout != 12) return PINN_ERR_LAYERS;
-    if ((rc = material_args(c, sums_out, sums_workspace, sums_ws_bytes))) return rc;
-    set_hooke(c, E, mu, rho, 1);
-    static_assert(PINN_MATERIAL_SUMS_NC3D == MATERIAL_SUMS_3D, "sums of the header and of the head");
-    if (c.n == 0) return (int)hipMemsetAsync(sums_out, 0, PINN_MATERIAL_SUMS_NC3D * sizeof(double), c.stream);
-    if (!impl) return fp32_call(c, HEAD_MATERIAL3D, 0, 5, 4, false);
-    return impl->nc3d_material(c);
+    Own o;
+    o.material(E, mu, rho, 1);
+    o.sums(sums_out, sums_workspace, sums_ws_bytes);
+    return point_call(CALL_NC3D_MATERIAL, params_flat, layers, n_layers, x, y, z, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 size_t pinn_field_error_workspace_bytes(int64_t n, int n_rows) {
@@ -803,57 +790,42 @@ int pinn_refine_keys(const float* score, int64_t n, const float* x, const float*
 int pinn_net_streams(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
                      const double lb[3], const double ub[3], int normalize, float* streams_out, int precision_mode, void* workspace,
                      size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (n > 0 && !streams_out) return PINN_ERR_NULL;
-    return run_forward(c, impl, streams_out, &Impl::streams, HEAD_FIELDS, 5);
+    Own o;
+    o.out = streams_out;
+    return point_call(CALL_NET_STREAMS, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_plate2d_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                            int64_t n, const double lb[3], const double ub[3], int normalize, const float* frozen_streams, double E,
                            double mu, double rho, const float term_weights[5], float* loss_terms_out, float* grad_flat_out,
                            int accumulate, int precision_mode, void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if ((n > 0 && !frozen_streams) || !term_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
-    if (c.net.nout != 5) return PINN_ERR_LAYERS;
-    set_hooke(c, E, mu, rho, 0);
-    for (int i = 0; i < 5; ++i) c.tw[i] = term_weights[i];
-    c.aux = frozen_streams;
-    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 5, &Impl::plate_loss_grad, HEAD_PLATE, 5);
+    Own o;
+    o.material(E, mu, rho, 0);
+    o.weights = term_weights;
+    o.aux = frozen_streams;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_PLATE_LOSS_GRAD, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_plate2d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
                                 int64_t n, const double lb[3], const double ub[3], int normalize, const float* frozen_streams, double E,
                                 double mu, double rho, const float term_weights[5], float* score_out, int precision_mode, void* workspace,
                                 size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (!term_weights || (n > 0 && (!frozen_streams || !score_out))) return PINN_ERR_NULL;
-    if (c.net.nout != 5) return PINN_ERR_LAYERS;
-    set_hooke(c, E, mu, rho, 0);
-    for (int i = 0; i < 5; ++i) c.tw[i] = term_weights[i];
-    c.aux = frozen_streams;
-    return run_forward(c, impl, score_out, &Impl::plate_score, HEAD_SCORE_PLATE, 5);
+    Own o;
+    o.material(E, mu, rho, 0);
+    o.weights = term_weights;
+    o.aux = frozen_streams;
+    o.out = score_out;
+    return point_call(CALL_PLATE_SCORE, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_plate2d_predict(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
                          const double lb[3], const double ub[3], int normalize, const float* frozen_streams, float* out, int precision_mode,
                          void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (n > 0 && (!frozen_streams || !out)) return PINN_ERR_NULL;
-    if (c.net.nout != 5) return PINN_ERR_LAYERS;
-    c.aux = frozen_streams;
-    return run_forward(c, impl, out, &Impl::plate_predict, HEAD_PREDICT_PLATE, 3);
+    Own o;
+    o.aux = frozen_streams;
+    o.out = out;
+    return point_call(CALL_PLATE_PREDICT, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_plate2d_traction_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y,
@@ -861,16 +833,11 @@ int pinn_plate2d_traction_loss_grad(const float* params_flat, const int* layers,
                                     const float* frozen_and_normals, const float weights[2], float* loss_terms_out,
                                     float* grad_flat_out, int accumulate, int precision_mode, void* workspace, size_t ws_bytes,
                                     void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if ((n > 0 && !frozen_and_normals) || !weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
-    if (c.net.nout != 5) return PINN_ERR_LAYERS;
-    c.tw[0] = weights[0];
-    c.tw[1] = weights[1];
-    c.aux = frozen_and_normals;
-    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 2, &Impl::traction_loss_grad, HEAD_TRACTION, 1);
+    Own o;
+    o.weights = weights;
+    o.aux = frozen_and_normals;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_TRACTION_LOSS_GRAD, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_plate2d_step(float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
@@ -928,15 +895,11 @@ int pinn_stream_loss_grad(const float* params_flat, const int* layers, int n_lay
                           int64_t n, const double lb[3], const double ub[3], int normalize, const float* targets,
                           const float* weights, float* loss_terms_out, float* grad_flat_out, int accumulate, int precision_mode,
                           void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
-    if (rc) return rc;
-    if (!weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
-    for (int s = 0; s < 5; ++s)
-        for (int o = 0; o < c.net.nout; ++o) c.w5[s][o] = weights[s * c.net.nout + o];
-    c.aux = targets;
-    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, c.net.nout, &Impl::stream_loss_grad, HEAD_STREAMS, 5);
+    Own o;
+    o.weights = weights;
+    o.aux = targets;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_STREAM_LOSS_GRAD, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int n_layers, const pinn_stream_set* sets, int n_sets,
@@ -976,7 +939,7 @@ int pinn_stream_loss_grad_multi(const float* params_flat, const int* layers, int
             if ((rc = (int)hipMemsetAsync(ss.loss_out, 0, (size_t)c.net.nout * sizeof(float), c.stream))) return rc;
             continue;
         }
-        if ((rc = fp32_call(set_call(c, ss, wmax, first), HEAD_STREAMS, c.net.nout, 5))) return rc;
+        if ((rc = fp32_call(set_call(c, ss, wmax, first), CALLS[CALL_STREAM_LOSS_GRAD]))) return rc;
         first = false;
     }
     if (first && !accumulate) return (int)hipMemsetAsync(grad_flat_out, 0, (size_t)c.net.nparams * sizeof(float), c.stream);
@@ -988,55 +951,41 @@ int pinn_nc3d_loss_grad(const float* params_flat, const int* layers, int n_layer
                         const float* t, int64_t n, const double lb[4], const double ub[4], int normalize, double E, double mu, double rho,
                         const float term_weights[12], float* loss_terms_out, float* grad_flat_out, int accumulate, int precision_mode,
                         void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
-    if (rc) return rc;
-    if (!term_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
-    if (c.net.nout != 12) return PINN_ERR_LAYERS;
-    set_hooke(c, E, mu, rho, 1);
-    for (int i = 0; i < 12; ++i) c.tw[i] = term_weights[i];
-    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, 12, &Impl::nc3d_loss_grad, HEAD_NC3D, 5, 4);
+    Own o;
+    o.material(E, mu, rho, 1);
+    o.weights = term_weights;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_NC3D_LOSS_GRAD, params_flat, layers, n_layers, x, y, z, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_nc3d_residual_score(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
                              const float* t, int64_t n, const double lb[4], const double ub[4], int normalize, double E, double mu, double rho,
                              const float term_weights[12], float* score_out, int precision_mode, void* workspace, size_t ws_bytes,
                              void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
-    if (rc) return rc;
-    if (!term_weights || (n > 0 && !score_out)) return PINN_ERR_NULL;
-    if (c.net.nout != 12) return PINN_ERR_LAYERS;
-    set_hooke(c, E, mu, rho, 1);
-    for (int i = 0; i < 12; ++i) c.tw[i] = term_weights[i];
-    return run_forward(c, impl, score_out, &Impl::nc3d_score, HEAD_SCORE3D, 5, 4);
+    Own o;
+    o.material(E, mu, rho, 1);
+    o.weights = term_weights;
+    o.out = score_out;
+    return point_call(CALL_NC3D_SCORE, params_flat, layers, n_layers, x, y, z, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_nc3d_data_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
                              const float* t, int64_t n, const double lb[4], const double ub[4], int normalize, const float* targets,
                              const float* out_weights, float* loss_terms_out, float* grad_flat_out, int accumulate, int precision_mode,
                              void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
-    if (rc) return rc;
-    if (!out_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
-    for (int i = 0; i < c.net.nout; ++i) c.tw[i] = out_weights[i];
-    c.targets = targets;
-    return run_loss_grad(c, impl, loss_terms_out, grad_flat_out, accumulate, c.net.nout, &Impl::nc3d_data_loss_grad, HEAD_DATA3D, 1, 4);
+    Own o;
+    o.weights = out_weights;
+    o.targets = targets;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_NC3D_DATA_LOSS_GRAD, params_flat, layers, n_layers, x, y, z, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_nc3d_fields(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* z,
                      const float* t, int64_t n, const double lb[4], const double ub[4], int normalize, float* fields_out, int precision_mode,
                      void* workspace, size_t ws_bytes, void* stream) {
-    Call c;
-    const Impl* impl = nullptr;
-    int rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl, 4, z);
-    if (rc) return rc;
-    if (n > 0 && !fields_out) return PINN_ERR_NULL;
-    return run_forward(c, impl, fields_out, &Impl::nc3d_fields, HEAD_FIELDS3D, 5, 4);
+    Own o;
+    o.out = fields_out;
+    return point_call(CALL_NC3D_FIELDS, params_flat, layers, n_layers, x, y, z, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
 }
 
 int pinn_adam_step(float* params_flat, float* m, float* v, const float* grad_flat, int64_t n_params, double lr, double beta1,

@@ -276,6 +276,10 @@ __host__ __device__ constexpr int material_sums_of(int head) {
 }
 __host__ __device__ constexpr bool head_is_score(int head) { return head == HEAD_SCORE || head == HEAD_SCORE_PLATE || head == HEAD_SCORE3D; }
 __host__ __device__ constexpr bool head_is_predict(int head) { return head == HEAD_PREDICT || head == HEAD_PREDICT_PLATE; }
+// heads that run the forward only: no adjoint panels, no loss sums, no gradient
+__host__ __device__ constexpr bool head_is_forward_only(int head) {
+    return head == HEAD_FIELDS || head == HEAD_FIELDS3D || head_is_score(head) || head_is_predict(head) || head_is_material(head);
+}
 constexpr int LOSS_SLOTS_3D = 16;     // per-wave loss partials: 8 slots for the reference's heads, 16 for the 3-D ones
 
 struct ChainArgs {
@@ -737,7 +741,7 @@ struct Chain {
         const int wpb = blockDim.x >> 6;
         const long gwave = (long)blockIdx.x * wpb + (threadIdx.x >> 6), nwaves = (long)gridDim.x * wpb;
         const int nl = a.net.nl;
-        constexpr bool FWD_ONLY = HEAD == HEAD_FIELDS || HEAD == HEAD_FIELDS3D || head_is_score(HEAD) || head_is_predict(HEAD) || head_is_material(HEAD);
+        constexpr bool FWD_ONLY = head_is_forward_only(HEAD);
         constexpr bool SPILL = !FWD_ONLY;
         __shared__ __attribute__((aligned(16))) char spill_lds[4 * 1024];      // one 1 KB transpose record per wave (256-thread blocks)
         char* rec = spill_lds + (threadIdx.x >> 6) * 1024;

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <utility>
+
 #include "../../include/pinn_hip.h"
 #include "pinn_device.hpp"
 #include "pinn_fused.hpp"
@@ -56,48 +58,50 @@ struct StreamSet {              // one stream-target point set of pinn_stream_lo
     float* loss_out;
 };
 
+// Every member has a default: `Call c;` is a call with no points, no outputs, zero constants and weights, and the library's defaults;
+// prepare() (pinn_capi.hip) and the entry points fill in what they are given.
 struct Call {
-    NetDesc net;
-    const float* params;
-    const float* x;
-    const float* y;
-    const float* t;
-    const float* z;            // 4-input heads only (input order x, y, z, t)
-    long n;
-    float sx[4], ox[4];        // input map; 4-input heads: index 2 = z, 3 = t
-    void* ws;
-    size_t ws_bytes;
-    hipStream_t stream;
-    float* loss_out;
-    float* grad_out;
-    int accumulate;
+    NetDesc net = {};
+    const float* params = nullptr;
+    const float* x = nullptr;
+    const float* y = nullptr;
+    const float* t = nullptr;
+    const float* z = nullptr;  // 4-input heads only (input order x, y, z, t)
+    long n = 0;
+    float sx[4] = {}, ox[4] = {};      // input map; 4-input heads: index 2 = z, 3 = t
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    hipStream_t stream = nullptr;
+    float* loss_out = nullptr;
+    float* grad_out = nullptr;
+    int accumulate = 0;
     // wave residual head
-    float c1, c2, G, rho;
-    float tw[16];
+    float c1 = 0.0f, c2 = 0.0f, G = 0.0f, rho = 0.0f;
+    float tw[16] = {};
     // data head
-    const float* targets;
-    int nsets;                 // > 0: pinn_data_loss_grad_multi -- the value-only sets of this call (else the single set x, y, t, n, targets, tw)
-    DataSet sets[4];
+    const float* targets = nullptr;
+    int nsets = 0;             // > 0: pinn_data_loss_grad_multi -- the value-only sets of this call (else the single set x, y, t, n, targets, tw)
+    DataSet sets[4] = {};
     // fields head
-    float* fields_out;
+    float* fields_out = nullptr;
     // material heads (pinn_*_material_sums): per-wave records, material_sums_of(head) doubles each, and the sums
     double* moment_part = nullptr;
     double* moment_out = nullptr;
     // plate / traction / stream-target heads
-    const float* aux;
-    float w5[5][8];
+    const float* aux = nullptr;
+    float w5[5][8] = {};
     float w5_norm = 0.0f;      // > 0: the stream-target weights are normalised by this value instead of their own maximum (a set of pinn_stream_loss_grad_multi)
     int n_ssets = 0;           // pinn_stream_loss_grad_multi: the call's sets
-    StreamSet ssets[PINN_MAX_STREAM_SETS];
+    StreamSet ssets[PINN_MAX_STREAM_SETS] = {};
     // optional per-kernel timing (host pointer, 4 floats: repack, chain, wgrad, reductions) -- makes the call synchronous
-    float* prof_ms;
-    ProfRing* ring;            // optional asynchronous launch timing (see ProfRing)
-    unsigned long long* dbg_stamps;   // optional device buffer for the fused kernel's phase timestamps (128 x u64)
-    int adj_shift;             // PINN_ADJOINT_SHIFT(k): adjoint seeds scaled by 2^-k inside the kernels, the gradient by 2^k at the reduction
-    int weights_packed;        // skip the repack: the workspace already holds the packed form of `params` (same net / precision mode)
-    int use_fused;             // 1: prefer the fused kernel where it applies (default), 0: force the two-kernel path
-    int one_stream_head;       // single-set one-stream calls: 0 = data head, 1 = hole traction (fused one-stream kernel, see DataSet::head)
-    int fast_state;            // PINN_FLAG_STATE_FP16: fused kernel parks its states as fp16 high parts only (faster, less accurate at trained weights)
+    float* prof_ms = nullptr;
+    ProfRing* ring = nullptr;  // optional asynchronous launch timing (see ProfRing)
+    unsigned long long* dbg_stamps = nullptr;      // optional device buffer for the fused kernel's phase timestamps (128 x u64)
+    int adj_shift = 0;         // PINN_ADJOINT_SHIFT(k): adjoint seeds scaled by 2^-k inside the kernels, the gradient by 2^k at the reduction
+    int weights_packed = 0;    // skip the repack: the workspace already holds the packed form of `params` (same net / precision mode)
+    int use_fused = 1;         // 1: prefer the fused kernel where it applies (default), 0: force the two-kernel path
+    int one_stream_head = 0;   // single-set one-stream calls: 0 = data head, 1 = hole traction (fused one-stream kernel, see DataSet::head)
+    int fast_state = 0;        // PINN_FLAG_STATE_FP16: fused kernel parks its states as fp16 high parts only (faster, less accurate at trained weights)
 };
 
 // paths taken by the loss + gradient calls of this process (pinn_debug_path_counts); defined in pinn_capi.hip
@@ -108,37 +112,81 @@ bool xcd_tail_device_ok();      // (pinn_capi.hip) the tail's premises hold on t
 // testing hook (pinn_debug_set_fused_grid_cap): at most this many workgroups in a fused launch (0: no cap beyond FUSED_GRID)
 extern int g_fused_grid_cap;
 
+// ---- The single-set per-point calls of the library, said ONCE: one id per call and one row of CALLS with everything the host knows about it.
+// Host::run<ID> builds the call's launch sequence from its row, Impl carries one run per id, and the entry points of pinn_capi.hip take
+// the streams, inputs, terms and output count of their checks and of the PINN_PREC_FP32 path from the same row.  The key is the call, not the
+// head: HEAD_FIELDS serves the fields (4 streams) and the streams (5), HEAD_DATA and HEAD_TRACTION both take the one-stream fused kind.
+enum CallId {
+    CALL_WAVE_LOSS_GRAD, CALL_DATA_LOSS_GRAD, CALL_WAVE_FIELDS, CALL_WAVE_SCORE, CALL_WAVE_PREDICT, CALL_WAVE_MATERIAL,
+    CALL_NET_STREAMS, CALL_PLATE_LOSS_GRAD, CALL_PLATE_SCORE, CALL_PLATE_PREDICT, CALL_PLATE_MATERIAL, CALL_TRACTION_LOSS_GRAD, CALL_STREAM_LOSS_GRAD,
+    CALL_NC3D_LOSS_GRAD, CALL_NC3D_SCORE, CALL_NC3D_DATA_LOSS_GRAD, CALL_NC3D_FIELDS, CALL_NC3D_MATERIAL, N_CALLS
+};
+// LOSS_GRAD: the fused kernel of the row's kind where it applies, else chain + weight-gradient kernels (loss sums and gradient);
+// FORWARD: one chain launch of a forward-only head that writes per point; FORWARD_SUMS: the same + the one-workgroup fp64 final sum of the
+// material heads' per-wave records
+enum CallShape { SHAPE_LOSS_GRAD, SHAPE_FORWARD, SHAPE_FORWARD_SUMS };
+// The predict heads (3 streams, forward only) run ONE block per wave at every width.  Measured at padded width 64, f16x3, 1 M points
+// (profiles/predict_head_calls.txt): two blocks need 230 + 256 registers and leave one wave per SIMD -- wave 8 x 64 0.92 ms, plate 0.94 ms --,
+// one block 0.82 / 0.80 ms; the wider nets have one block in every head.
+constexpr int NB_PREDICT = 1;
+struct CallRow {
+    int id;                    // its own CallId (held to its place in CALLS below)
+    int head;                  // HEAD_* of chain_kernel and fp32_chain_kernel
+    int ns;                    // streams
+    int din;                   // inputs: 3 (x, y, t) or 4 (x, y, z, t)
+    int nout;                  // outputs the net must have (0: any)
+    int nterms;                // loss terms = term weights the call takes (0: the net's outputs; none for a forward-only head that reads no weights)
+    int shape;                 // CallShape
+    bool split_only;           // compiled for the split-precision lines only (the five-stream and 4-input kernels): PINN_ERR_PRECISION elsewhere
+    bool with_tw;              // the head reads the call's term weights (c.tw; HEAD_STREAMS: c.w5): a required argument; the other heads see zeros
+    bool needs_aux;            // the head reads c.aux at every point (frozen streams, hole normals): a required argument of a call with points
+    int nb;                    // blocks per wave of the chain launch (0: Host::nb<ns>())
+    bool fused;                // a loss + gradient call that takes the fused kernel of kind <ns, din> where one is compiled for the net (with_fused)
+    bool one_stream_head;      // the one-stream fused kernel runs it as a hole-traction set (Call::one_stream_head)
+    bool counted;              // a PINN_PREC_FP32 run of it counts in g_path_counts (a loss + gradient call; historically also fields and streams)
+};
+constexpr CallRow CALLS[N_CALLS] = {
+    //                        head                 ns din nout terms shape               split  tw     aux    nb          fused  1-str  counted
+    {CALL_WAVE_LOSS_GRAD,     HEAD_WAVE,           4, 3,  7,   7,    SHAPE_LOSS_GRAD,    false, true,  false, 0,          true,  false, true},
+    {CALL_DATA_LOSS_GRAD,     HEAD_DATA,           1, 3,  0,   0,    SHAPE_LOSS_GRAD,    false, true,  false, 0,          true,  false, true},
+    {CALL_WAVE_FIELDS,        HEAD_FIELDS,         4, 3,  0,   0,    SHAPE_FORWARD,      false, false, false, 0,          false, false, true},
+    {CALL_WAVE_SCORE,         HEAD_SCORE,          4, 3,  7,   7,    SHAPE_FORWARD,      false, true,  false, 0,          false, false, false},
+    {CALL_WAVE_PREDICT,       HEAD_PREDICT,        3, 3,  7,   0,    SHAPE_FORWARD,      false, false, false, NB_PREDICT, false, false, false},
+    {CALL_WAVE_MATERIAL,      HEAD_MATERIAL,       4, 3,  7,   0,    SHAPE_FORWARD_SUMS, false, false, false, 0,          false, false, false},
+    {CALL_NET_STREAMS,        HEAD_FIELDS,         5, 3,  0,   0,    SHAPE_FORWARD,      true,  false, false, 0,          false, false, true},
+    {CALL_PLATE_LOSS_GRAD,    HEAD_PLATE,          5, 3,  5,   5,    SHAPE_LOSS_GRAD,    true,  true,  true,  0,          true,  false, true},
+    {CALL_PLATE_SCORE,        HEAD_SCORE_PLATE,    5, 3,  5,   5,    SHAPE_FORWARD,      true,  true,  true,  0,          false, false, false},
+    {CALL_PLATE_PREDICT,      HEAD_PREDICT_PLATE,  3, 3,  5,   0,    SHAPE_FORWARD,      true,  false, true,  NB_PREDICT, false, false, false},
+    {CALL_PLATE_MATERIAL,     HEAD_MATERIAL_PLATE, 5, 3,  5,   0,    SHAPE_FORWARD_SUMS, true,  false, true,  0,          false, false, false},
+    {CALL_TRACTION_LOSS_GRAD, HEAD_TRACTION,       1, 3,  5,   2,    SHAPE_LOSS_GRAD,    true,  true,  true,  0,          true,  true,  true},
+    {CALL_STREAM_LOSS_GRAD,   HEAD_STREAMS,        5, 3,  0,   0,    SHAPE_LOSS_GRAD,    true,  true,  false, 0,          false, false, true},
+    {CALL_NC3D_LOSS_GRAD,     HEAD_NC3D,           5, 4,  12,  12,   SHAPE_LOSS_GRAD,    true,  true,  false, 0,          true,  false, true},
+    {CALL_NC3D_SCORE,         HEAD_SCORE3D,        5, 4,  12,  12,   SHAPE_FORWARD,      true,  true,  false, 0,          false, false, false},
+    {CALL_NC3D_DATA_LOSS_GRAD, HEAD_DATA3D,        1, 4,  0,   0,    SHAPE_LOSS_GRAD,    true,  true,  false, 0,          true,  false, true},
+    {CALL_NC3D_FIELDS,        HEAD_FIELDS3D,       5, 4,  0,   0,    SHAPE_FORWARD,      true,  false, false, 0,          false, false, true},
+    {CALL_NC3D_MATERIAL,      HEAD_MATERIAL3D,     5, 4,  12,  0,    SHAPE_FORWARD_SUMS, true,  false, false, 0,          false, false, false},
+};
+constexpr bool calls_consistent() {
+    for (int i = 0; i < N_CALLS; ++i) {
+        const CallRow& r = CALLS[i];
+        if (r.id != i) return false;                                                            // every row in its id's place
+        if ((r.shape == SHAPE_LOSS_GRAD) == head_is_forward_only(r.head)) return false;        // the shape is the head's
+        if ((r.shape == SHAPE_FORWARD_SUMS) != head_is_material(r.head)) return false;
+        if ((r.din == 4) != head_is_3d(r.head)) return false;
+        if (r.with_tw != (r.shape == SHAPE_LOSS_GRAD || head_is_score(r.head))) return false;
+        if ((r.fused || r.one_stream_head) && r.shape != SHAPE_LOSS_GRAD) return false;
+    }
+    return true;
+}
+static_assert(calls_consistent(), "CALLS: a row out of its place, or one that contradicts its head");
+
 struct Impl {
+    int (*run[N_CALLS])(const Call&);      // the per-point calls, by CallId (Host::run<ID>)
     int (*path_for)(const NetDesc&, int head, size_t ws_bytes);
+    size_t (*ws_bytes)(const NetDesc&, long n, int minimum);
     int (*wave_step)(const Call&, const Call&, const AdamEpilogue&, int* rc);      // 1: ran (narrow fused layouts), 0: make the calls one by one
     int (*plate_step)(const Call&, const Call&, const AdamEpilogue&, int* rc);
-    int (*wave_loss_grad)(const Call&);
-    int (*data_loss_grad)(const Call&);
-    int (*fields)(const Call&);
-    size_t (*ws_bytes)(const NetDesc&, long n, int minimum);
-    // 5-stream family (second time derivative), compiled for the split-precision variants only
-    int (*plate_loss_grad)(const Call&);
-    int (*traction_loss_grad)(const Call&);
-    int (*stream_loss_grad)(const Call&);
-    int (*streams)(const Call&);
-    int (*stream_sets_loss_grad)(const Call&);      // pinn_stream_loss_grad_multi
-    // 4-input family (3-D Navier-Cauchy extension: value + 4 first-order streams, 12 outputs), split-precision variants only
-    int (*nc3d_loss_grad)(const Call&);
-    int (*nc3d_data_loss_grad)(const Call&);
-    int (*nc3d_fields)(const Call&);
-    // per-point residual score of the wave family (forward only, HEAD_SCORE)
-    int (*wave_score)(const Call&);
-    // the same for the plate family (HEAD_SCORE_PLATE, `aux` = frozen streams) and the 4-input family (HEAD_SCORE3D); split modes only
-    int (*plate_score)(const Call&);
-    int (*nc3d_score)(const Call&);
-    // predict heads (forward only, value + space tangents): HEAD_PREDICT every compiled line; HEAD_PREDICT_PLATE split modes only
-    int (*wave_predict)(const Call&);
-    int (*plate_predict)(const Call&);
-    // the fp64 residual and moment sums of the wave family (forward only, HEAD_MATERIAL + the one-workgroup final pass)
-    int (*wave_material)(const Call&);
-    // the same for the plate family (HEAD_MATERIAL_PLATE, `aux` = frozen streams) and the 4-input family (HEAD_MATERIAL3D); split modes only
-    int (*plate_material)(const Call&);
-    int (*nc3d_material)(const Call&);
+    int (*stream_sets_loss_grad)(const Call&);      // pinn_stream_loss_grad_multi (split-precision variants only)
     // pinn_debug_cache_policy: the collocation kernel compiled for this net and head (asked of the F16 split-3 line of the net's width)
     int (*cache_policy)(const NetDesc&, int head, size_t* images_bytes, size_t* sums_bytes);
 };
@@ -204,10 +252,6 @@ struct Host {
     // points per wave tile = 16*NB: two blocks for narrow nets, one when the register budget is tight (wide nets, 5 streams)
     template <int NS>
     static constexpr int nb() { return (WIDTH <= 64 && NS != 5) ? 2 : 1; }
-    // The predict heads (3 streams, forward only) run ONE block per wave at every width.  Measured at padded width 64, f16x3, 1 M points
-    // (profiles/predict_head_calls.txt): two blocks need 230 + 256 registers and leave one wave per SIMD -- wave 8 x 64 0.92 ms, plate 0.94 ms --,
-    // one block 0.82 / 0.80 ms; the wider nets have one block in every head.
-    static constexpr int NB_PREDICT = 1;
     static constexpr int NP = SPLIT == 3 ? 2 : 1;
     static constexpr int NPS = SPLIT == 3 ? 2 : 1;    // stored weight-fragment parts
     static constexpr int FUSED_PARTS = SPLIT == 3 ? 3 : 1;   // ... of the fused kernel's format (repack_kernel)
@@ -803,20 +847,12 @@ struct Host {
         });
     }
 
-    static int wave_loss_grad(const Call& c) {
-        int rc = 0;
-        if (c.use_fused && try_fused<4>(c, &rc, 7)) return rc;
-        return loss_grad<4, HEAD_WAVE>(c, 7);
-    }
-    static int data_loss_grad(const Call& c) {
-        int rc = 0;
-        if (c.use_fused && try_fused<1>(c, &rc, c.net.nout)) return rc;
-        if (c.nsets == 0) return loss_grad<1, HEAD_DATA>(c, c.net.nout);
-        // several sets on the two-kernel path: one after the other, accumulating into the same gradient
+    // several value-only sets on the two-kernel path: one after the other, accumulating into the same gradient
+    static int data_sets_loss_grad(const Call& c) {
         bool first = true;
         for (int k = 0; k < c.nsets; ++k) {
             if (c.sets[k].n <= 0) continue;
-            if ((rc = loss_grad<1, HEAD_DATA>(set_call(c, c.sets[k], first), c.net.nout))) return rc;
+            if (const int rc = loss_grad<1, HEAD_DATA>(set_call(c, c.sets[k], first), c.net.nout)) return rc;
             first = false;
         }
         return 0;
@@ -843,76 +879,42 @@ struct Host {
         hipLaunchKernelGGL((chain_kernel<Op, SPLIT, WIDTH, NB, NS, HEAD>), dim3(chain_blocks(ntiles)), dim3(256), 0, c.stream, a);
         return (int)hipGetLastError();
     }
-    // pinn_wave2d_predict / pinn_plate2d_predict: the strain streams only (value, d/dx, d/dy)
-    static int wave_predict(const Call& c) { return forward<3, HEAD_PREDICT, NB_PREDICT>(c, false); }
-    static int plate_predict(const Call& c) {
-        if constexpr (SPLIT == 3) return forward<3, HEAD_PREDICT_PLATE, NB_PREDICT>(c, false);
-        return PINN_ERR_PRECISION;
-    }
 
-    static int fields(const Call& c) { return forward<4, HEAD_FIELDS>(c, false); }
-    static int wave_score(const Call& c) { return forward<4, HEAD_SCORE>(c, true); }      // pinn_wave2d_residual_score
-    // pinn_plate2d_residual_score (`aux` = frozen streams) / pinn_nc3d_residual_score: five streams; split-precision variants only, like their loss calls
-    static int plate_score(const Call& c) {
-        if constexpr (SPLIT == 3) return forward<5, HEAD_SCORE_PLATE>(c, true);
-        return PINN_ERR_PRECISION;
-    }
-    static int nc3d_score(const Call& c) {
-        if constexpr (SPLIT == 3) return forward<5, HEAD_SCORE3D>(c, true);
-        return PINN_ERR_PRECISION;
-    }
-
-    // pinn_wave2d_material_sums: every wave of the chain launch writes its record (one without tiles writes zeros), then one workgroup adds
-    // the records in index order
-    static int wave_material(const Call& c) {
-        const int rc = forward<4, HEAD_MATERIAL>(c, false);
-        if (rc) return rc;
-        const int nrecords = chain_blocks(forward_tiles<nb<4>()>(c.n)) * 4;
-        static_assert(MAX_BLOCKS * 4 <= material::MAX_RECORDS, "records of the largest chain grid");
-        return material::launch_final<MATERIAL_SUMS>(c.moment_part, nrecords, c.moment_out, 0, c.stream);
-    }
-    // pinn_plate2d_material_sums / pinn_nc3d_material_sums: five streams; split-precision variants only, like their score calls
-    template <int HEAD>
-    static int family_material(const Call& c) {
-        if constexpr (SPLIT == 3) {
-            const int rc = forward<5, HEAD>(c, false);
-            if (rc) return rc;
-            const int nrecords = chain_blocks(forward_tiles<nb<5>()>(c.n)) * 4;
-            return material::launch_final<material_sums_of(HEAD)>(c.moment_part, nrecords, c.moment_out, 0, c.stream);
+    // ---- One per-point call, built from its row of CALLS.  A row that exists for the split modes only answers PINN_ERR_PRECISION on every
+    // other line of pinn_variants.def WITHOUT naming its kernels, so those lines do not compile the five-stream and 4-input instantiations.
+    template <int ID>
+    static int run(const Call& c) {
+        constexpr CallRow R = CALLS[ID];
+        if constexpr (R.split_only && SPLIT != 3) {
+            return PINN_ERR_PRECISION;
+        } else if constexpr (R.shape == SHAPE_LOSS_GRAD) {
+            const int nterms = R.nterms ? R.nterms : c.net.nout;
+            if constexpr (R.fused) {
+                int rc = 0;
+                if constexpr (R.one_stream_head) {
+                    Call t = c;      // the hole-traction set: the one-stream kernel's head takes the set's kind from the set table
+                    t.one_stream_head = 1;
+                    if (c.use_fused && try_fused<R.ns, R.din>(t, &rc, nterms)) return rc;
+                } else if (c.use_fused && try_fused<R.ns, R.din>(c, &rc, nterms)) {
+                    return rc;
+                }
+            }
+            if constexpr (R.head == HEAD_DATA) {
+                if (c.nsets > 0) return data_sets_loss_grad(c);      // (pinn_data_loss_grad_multi)
+            }
+            return loss_grad<R.ns, R.head>(c, nterms);
+        } else {
+            constexpr int NB = R.nb ? R.nb : nb<R.ns>();
+            const int rc = forward<R.ns, R.head, NB>(c, R.with_tw);
+            if constexpr (R.shape == SHAPE_FORWARD_SUMS) {
+                // every wave of the chain launch wrote its record (one without tiles writes zeros); one workgroup adds the records in index order
+                if (rc) return rc;
+                static_assert(MAX_BLOCKS * 4 <= material::MAX_RECORDS, "records of the largest chain grid");
+                return material::launch_final<material_sums_of(R.head)>(c.moment_part, chain_blocks(forward_tiles<NB>(c.n)) * 4, c.moment_out, 0, c.stream);
+            } else {
+                return rc;
+            }
         }
-        return PINN_ERR_PRECISION;
-    }
-    static int plate_material(const Call& c) { return family_material<HEAD_MATERIAL_PLATE>(c); }
-    static int nc3d_material(const Call& c) { return family_material<HEAD_MATERIAL3D>(c); }
-
-    // 5-stream family (plate): split-precision variants only
-    static int plate_loss_grad(const Call& c) {
-        if constexpr (SPLIT == 3) {
-            int rc = 0;
-            if (c.use_fused && try_fused<5>(c, &rc, 5)) return rc;      // padded width <= 64: five-stream instantiation of the fused kernel
-            return loss_grad<5, HEAD_PLATE>(c, 5);
-        }
-        return PINN_ERR_PRECISION;
-    }
-    static int traction_loss_grad(const Call& c) {
-        if constexpr (SPLIT == 3) {
-            // the hole-traction set through the one-stream instantiation of the fused kernel (its head takes the set's kind from the set
-            // table: round 4; the plate's last user of the two-kernel path)
-            int rc = 0;
-            Call t = c;
-            t.one_stream_head = 1;
-            if (c.use_fused && try_fused<1>(t, &rc, 2)) return rc;
-            return loss_grad<1, HEAD_TRACTION>(c, 2);
-        }
-        return PINN_ERR_PRECISION;
-    }
-    static int stream_loss_grad(const Call& c) {
-        if constexpr (SPLIT == 3) return loss_grad<5, HEAD_STREAMS>(c, c.net.nout);
-        return PINN_ERR_PRECISION;
-    }
-    static int streams(const Call& c) {
-        if constexpr (SPLIT == 3) return forward<5, HEAD_FIELDS>(c, false);
-        return PINN_ERR_PRECISION;
     }
 
     // ---- pinn_stream_loss_grad_multi: the stream-target sets of a pre-training loss in one launch of fused_sets_kernel
@@ -994,33 +996,20 @@ struct Host {
         }
         return PINN_ERR_PRECISION;
     }
-    // 4-input family (two-kernel path; the fused kernel covers the reference's 3-input nets only)
-    static int nc3d_loss_grad(const Call& c) {
-        if constexpr (SPLIT == 3) {
-            int rc = 0;
-            if (c.use_fused && (try_fused<5, 4>(c, &rc, 12))) return rc;
-            return loss_grad<5, HEAD_NC3D>(c, 12);
-        }
-        return PINN_ERR_PRECISION;
+    template <int... ID>
+    static Impl make_impl(std::integer_sequence<int, ID...>) {
+        Impl I = {};
+        ((I.run[ID] = &run<ID>), ...);
+        I.path_for = &path_for;
+        I.ws_bytes = &ws_bytes;
+        I.wave_step = &wave_step;
+        I.plate_step = &plate_step;
+        I.stream_sets_loss_grad = &stream_sets_loss_grad;
+        I.cache_policy = &cache_policy;
+        return I;
     }
-    static int nc3d_data_loss_grad(const Call& c) {
-        if constexpr (SPLIT == 3) {
-            int rc = 0;
-            if (c.use_fused && (try_fused<1, 4>(c, &rc, 12))) return rc;
-            return loss_grad<1, HEAD_DATA3D>(c, c.net.nout);
-        }
-        return PINN_ERR_PRECISION;
-    }
-    static int nc3d_fields(const Call& c) {
-        if constexpr (SPLIT == 3) return forward<5, HEAD_FIELDS3D>(c, false);
-        return PINN_ERR_PRECISION;
-    }
-
     static const Impl* impl() {
-        static const Impl I = {&path_for, &wave_step, &plate_step, &wave_loss_grad, &data_loss_grad, &fields, &ws_bytes,
-                               &plate_loss_grad, &traction_loss_grad, &stream_loss_grad, &streams, &stream_sets_loss_grad,
-                               &nc3d_loss_grad, &nc3d_data_loss_grad, &nc3d_fields, &wave_score, &plate_score, &nc3d_score,
-                               &wave_predict, &plate_predict, &wave_material, &plate_material, &nc3d_material, &cache_policy};
+        static const Impl I = make_impl(std::make_integer_sequence<int, N_CALLS>());
         return &I;
     }
 };
