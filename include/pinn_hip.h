@@ -84,7 +84,8 @@ enum {
     PINN_ERR_PRECISION = -3,   /* unknown precision_mode */
     PINN_ERR_WORKSPACE = -4,   /* workspace smaller than pinn_min_workspace_bytes() or misaligned */
     PINN_ERR_SIZE = -5,        /* n < 0 (n == 0 is a valid empty batch: zero sums, zero / untouched gradient); pinn_select_k: n >= 2^31 or k outside 0 .. n;
-                                  pinn_sample_box / pinn_refine_keys: n >= 2^31, n_balls outside 0 .. PINN_MAX_BALLS, a ball's ndim outside {2, 3} */
+                                  pinn_sample_box / pinn_refine_keys: n >= 2^31, n_balls outside 0 .. PINN_MAX_BALLS, a ball's ndim outside {2, 3};
+                                  pinn_binned_sums / pinn_causal_cdf / pinn_sample_box_cdf: n >= 2^31, n_bins outside 1 .. PINN_MAX_TIME_BINS, a bad range, eps or floor */
     PINN_ERR_COLLECTIVE = -6,  /* pinn_p2p_*: not connected; a coarse-grained buffer across devices (pinn_p2p_connect); or a rank did not arrive within the
                                 * bounded wait of some call (pinn_p2p_set_timeout_ms, default 30 s) -- that call's buffer is then NaN on this rank */
     PINN_ERR_RANGE = -7,       /* pinn_wave2d_loss_grad_checked: gradient non-finite even on the two-kernel path with the reverse pass scaled by 2^-24 */
@@ -329,6 +330,64 @@ int pinn_refine_keys(const float* score, int64_t n, const float* x, const float*
                      const pinn_ball* balls, int n_balls, int mode, double power, double c,
                      uint64_t seed, uint32_t stream_id, uint64_t first,
                      float* key_out, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- causal collocation sampling: time-binned score sums, the causal weights and their CDF, a box draw that follows it ---------------------
+ * A loss with 1/N weights over points drawn with density ~ w(t) estimates the causally weighted loss of Wang, Sankaran and Perdikaris
+ * ("Respecting causality is all you need"): w of a time slice = exp(-eps * accumulated residual of all earlier slices).  The three calls turn
+ * per-point scores (pinn_wave2d_residual_score, masked by pinn_refine_keys) into such a set without a host round trip. */
+#define PINN_MAX_TIME_BINS 64
+
+/* Per-bin sums of `value` over n_bins equal bins of [lo, hi] of `coord`.  value, coord are DEVICE arrays of n floats; sums_out is a DEVICE array
+ * of 2 * n_bins doubles, [2][n_bins]: the sum of value over the points of each bin, then their count (a double, exact).
+ *   bin      all in fp32, so that numpy float32 reproduces it bit for bit:  d = coord - (float)lo;  q = d * scale  with
+ *            scale = (float)(n_bins / (hi - lo)), the quotient taken in double;  b = (int)floorf(q), clamped to 0 .. n_bins - 1 (points
+ *            outside [lo, hi] count in the first / last bin)
+ *   skipped  neither summed nor counted: a point whose value is negative, not finite or NaN, or whose coord is NaN -- the -inf keys of
+ *            PINN_KEYS_MASK keep excluded balls out of the profile this way
+ * Values widen to fp64 before the first addition.  Determinism: per-workgroup partial records over contiguous index ranges, each walked in
+ * a fixed order, added by one final pass in a fixed order (the scheme of pinn_field_error_sums); no floating-point atomics; the output is a
+ * function of the arguments alone.
+ * No host synchronisation; n == 0 writes zeros.
+ * `workspace` is device memory of pinn_binned_sums_workspace_bytes(n, n_bins) bytes (0 for arguments the call rejects), 256-byte aligned.
+ * Errors: n < 0, n >= 2^31, n_bins outside 1 .. PINN_MAX_TIME_BINS, or lo / hi not finite with hi > lo: PINN_ERR_SIZE; a NULL array that is
+ * needed: PINN_ERR_NULL; short or misaligned workspace: PINN_ERR_WORKSPACE. */
+size_t pinn_binned_sums_workspace_bytes(int64_t n, int n_bins);
+int pinn_binned_sums(const float* value, const float* coord, int64_t n, double lo, double hi, int n_bins,
+                     double* sums_out, void* workspace, size_t ws_bytes, void* stream);
+
+/* The causal weights of the bins and the CDF of their density, from the [2][n_bins] output of pinn_binned_sums (`binned`, DEVICE).  w_out is
+ * a DEVICE array of n_bins doubles, cdf_out a DEVICE array of n_bins + 1 floats.  In fp64, B = n_bins:
+ *   m_b   = sum_b / count_b  (0 where the count is 0)
+ *   c_0   = 0,  c_b = c_(b-1) + m_(b-1)  in ascending order
+ *   w_b   = exp(-eps * c_b),  so w_0 = 1 exactly
+ *   d_b   = max(w_b, floor)
+ *   cdf_0 = 0,  cdf_b = (float)((d_0 + .. + d_(b-1)) / (d_0 + .. + d_(B-1)))  with the sums in ascending order,  cdf_B = 1 set explicitly
+ * An entry that would come out below its predecessor after rounding, or is no number, takes the predecessor's value: the table never
+ * decreases and holds no NaN.  floor = 1 or eps = 0 give the uniform table b / B (exact for B a power of two).  A floor above 1 is used as 1:
+ * no w_b exceeds 1, so the densities are equal either way, and their sum cannot overflow however large the floor.
+ * One small launch, no workspace, no host synchronisation.
+ * Errors: n_bins outside 1 .. PINN_MAX_TIME_BINS, eps < 0, floor < 0 or either not finite: PINN_ERR_SIZE; a NULL array: PINN_ERR_NULL. */
+int pinn_causal_cdf(const double* binned, int n_bins, double eps, double floor,
+                    double* w_out, float* cdf_out, void* stream);
+
+/* pinn_sample_box with the LAST column (t) drawn from the piecewise-constant density that t_cdf encodes over n_bins equal bins of
+ * [lo_t, hi_t]; t_cdf is a DEVICE array of n_bins + 1 floats, t_cdf[0] = 0, t_cdf[n_bins] = 1, never decreasing (pinn_causal_cdf's cdf_out).
+ * The call reads the same Philox block (last counter word 0) and the same words: the space columns are bit-identical to pinn_sample_box's
+ * for the same (seed, stream_id, first + i).  The time column uses the word it always used:
+ *   u = (r >> 8) * 2^-24
+ *   b = the largest index in 0 .. n_bins - 1 with t_cdf[b] <= u  -- a bin of zero width is never chosen
+ *   f = min((u - t_cdf[b]) / (t_cdf[b+1] - t_cdf[b]), 1)  in fp32, IEEE division
+ *   s = ((float)b + f) / (float)n_bins
+ *   t = min(fma(s, (float)(hi_t - lo_t), (float)lo_t), (float)hi_t)  -- ONE fma, as the box call
+ * With the uniform table b / B, B a power of two, every step of the inverse is exact (u B - b and the divisions by powers of two round
+ * nothing), s == u, and ALL columns are bit-identical to pinn_sample_box's.  A point is a function of (seed, stream_id, idx, lo, hi) and the
+ * table alone, whatever the grid, so the call (first + m, n - m) gives the tail of the call (first, n).  One launch (the table is staged in
+ * LDS once per workgroup, the search is at most 6 steps), no workspace, no host synchronisation; n == 0 is a valid no-op.
+ * Errors: n < 0, n >= 2^31 or n_bins outside 1 .. PINN_MAX_TIME_BINS: PINN_ERR_SIZE; dim outside {3, 4}: PINN_ERR_LAYERS; a NULL array (t_cdf
+ * included, whatever n): PINN_ERR_NULL. */
+int pinn_sample_box_cdf(uint64_t seed, uint32_t stream_id, uint64_t first, int64_t n, int dim,
+                        const double lo[4], const double hi[4], const float* t_cdf, int n_bins,
+                        float* x, float* y, float* z, float* t, void* stream);
 
 /* ---- plate-with-hole family (PLATE = PlateHoleQuarter/train/train.py); precision_mode must be a split mode ---------------
  * Streams of one net at raw or normalised (x,y,t): streams_out is SoA [5][n_out][n] = Y, dY/dx, dY/dy, dY/dt, d2Y/dt2.

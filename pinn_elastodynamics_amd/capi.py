@@ -49,6 +49,7 @@ class StreamSet(C.Structure):
 
 
 MAX_BALLS = 4                      # PINN_MAX_BALLS
+MAX_TIME_BINS = 64                 # PINN_MAX_TIME_BINS
 MATERIAL_SUMS = 14                 # PINN_MATERIAL_SUMS
 MATERIAL_SUMS_PLATE = 12           # PINN_MATERIAL_SUMS_PLATE
 MATERIAL_SUMS_NC3D = 24            # PINN_MATERIAL_SUMS_NC3D
@@ -147,6 +148,10 @@ PROTOTYPES = {
     "pinn_sample_box": (_i32, [_u64, _u32, _u64, _i64, _i32, _pf64, _pf64, _vp, _vp, _vp, _vp, _vp]),
     "pinn_refine_keys_workspace_bytes": (_sz, [_i64]),
     "pinn_refine_keys": (_i32, [_vp, _i64, _vp, _vp, _vp, C.POINTER(Ball), _i32, _i32, _f64, _f64, _u64, _u32, _u64, _vp, _vp, _sz, _vp]),
+    "pinn_binned_sums_workspace_bytes": (_sz, [_i64, _i32]),
+    "pinn_binned_sums": (_i32, [_vp, _vp, _i64, _f64, _f64, _i32, _vp, _vp, _sz, _vp]),
+    "pinn_causal_cdf": (_i32, [_vp, _i32, _f64, _f64, _vp, _vp, _vp]),
+    "pinn_sample_box_cdf": (_i32, [_u64, _u32, _u64, _i64, _i32, _pf64, _pf64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pinn_net_streams": (_i32, _NET + _PTS3 + [_vp] + _TAIL),
     "pinn_plate2d_loss_grad": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32] + _OUT + _TAIL),
     "pinn_plate2d_residual_score": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32, _vp] + _TAIL),
@@ -459,12 +464,27 @@ class PinnLib:
     def select_k(self, score, n, k, largest, idx_out, ws, ws_bytes, stream=0):
         self.call("pinn_select_k", score, int(n), int(k), int(bool(largest)), idx_out, ws, int(ws_bytes), stream)
 
-    def sample_box(self, seed, stream_id, first, n, lo, hi, cols, stream=0):
-        """pinn_sample_box.  cols: the 3 (x, y, t) or 4 (x, y, z, t) device pointers; lo / hi: as many bounds."""
+    def sample_box(self, seed, stream_id, first, n, lo, hi, cols, stream=0, t_cdf=None, n_bins=0):
+        """pinn_sample_box.  cols: the 3 (x, y, t) or 4 (x, y, z, t) device pointers; lo / hi: as many bounds.  With ``t_cdf`` (a device
+        pointer to n_bins + 1 floats): pinn_sample_box_cdf, the time column drawn from that table."""
         dim = len(cols)
         x, y, z, t = (cols[0], cols[1], None, cols[2]) if dim == 3 else (tuple(cols) + (None,) * 4)[:4]
         d4 = lambda v: (C.c_double * 4)(*([float(a) for a in v] + [0.0] * 4)[:4])
-        self.call("pinn_sample_box", int(seed), int(stream_id), int(first), int(n), dim, d4(lo), d4(hi), x, y, z, t, stream)
+        if t_cdf is None:
+            self.call("pinn_sample_box", int(seed), int(stream_id), int(first), int(n), dim, d4(lo), d4(hi), x, y, z, t, stream)
+        else:
+            self.call("pinn_sample_box_cdf", int(seed), int(stream_id), int(first), int(n), dim, d4(lo), d4(hi), t_cdf, int(n_bins), x, y, z, t, stream)
+
+    def binned_sums_workspace_bytes(self, n, n_bins) -> int:
+        return int(self.lib.pinn_binned_sums_workspace_bytes(int(n), int(n_bins)))
+
+    def binned_sums(self, value, coord, n, lo, hi, n_bins, sums_out, ws, ws_bytes, stream=0):
+        """pinn_binned_sums: sums_out (device, 2 * n_bins doubles) = per bin of [lo, hi] the sum of value, then the count"""
+        self.call("pinn_binned_sums", value, coord, int(n), float(lo), float(hi), int(n_bins), sums_out, ws, int(ws_bytes), stream)
+
+    def causal_cdf(self, binned, n_bins, eps, floor, w_out, cdf_out, stream=0):
+        """pinn_causal_cdf: w_out (device, n_bins doubles), cdf_out (device, n_bins + 1 floats) from the output of binned_sums"""
+        self.call("pinn_causal_cdf", binned, int(n_bins), float(eps), float(floor), w_out, cdf_out, stream)
 
     def refine_keys_workspace_bytes(self, n) -> int:
         return int(self.lib.pinn_refine_keys_workspace_bytes(int(n)))

@@ -6,6 +6,7 @@
 #include "pinn_select.hpp"
 #include "pinn_sample.hpp"
 #include "pinn_validate.hpp"
+#include "pinn_causal.hpp"
 
 #ifndef PINN_VARIANTS_DEF
 #define PINN_VARIANTS_DEF "pinn_variants.def"     // experiments (tools/exp_build.sh) build a one-variant library
@@ -785,6 +786,46 @@ int pinn_refine_keys(const float* score, int64_t n, const float* x, const float*
     a.stream_id = stream_id;
     a.key_out = key_out;
     return sample::launch_keys(a, mode == PINN_KEYS_SAMPLE, workspace, static_cast<hipStream_t>(stream));
+}
+
+static bool bad_bins(int64_t n, int n_bins) { return n < 0 || n >= (int64_t)1 << 31 || n_bins < 1 || n_bins > PINN_MAX_TIME_BINS; }
+
+size_t pinn_binned_sums_workspace_bytes(int64_t n, int n_bins) { return bad_bins(n, n_bins) ? 0 : causal::ws_bytes(n_bins); }
+
+int pinn_binned_sums(const float* value, const float* coord, int64_t n, double lo, double hi, int n_bins, double* sums_out, void* workspace,
+                     size_t ws_bytes, void* stream) {
+    static_assert(PINN_MAX_TIME_BINS == causal::MAX_BINS, "pinn_hip.h and pinn_causal.hpp disagree");
+    if (bad_bins(n, n_bins) || !(hi - lo > 0.0) || !std::isfinite(hi - lo) || !std::isfinite(lo)) return PINN_ERR_SIZE;
+    if (!sums_out || !workspace || (n > 0 && (!value || !coord))) return PINN_ERR_NULL;
+    if (((uintptr_t)workspace & 255) != 0 || ws_bytes < causal::ws_bytes(n_bins)) return PINN_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) return (int)hipMemsetAsync(sums_out, 0, (size_t)2 * n_bins * sizeof(double), st);
+    causal::BinArgs a;
+    a.value = value;
+    a.coord = coord;
+    a.n = (uint32_t)n;
+    a.lo = (float)lo;
+    a.scale = (float)((double)n_bins / (hi - lo));
+    a.n_bins = n_bins;
+    a.sums_out = sums_out;
+    return causal::launch_bins(a, workspace, st);
+}
+
+int pinn_causal_cdf(const double* binned, int n_bins, double eps, double floor, double* w_out, float* cdf_out, void* stream) {
+    if (n_bins < 1 || n_bins > PINN_MAX_TIME_BINS || !(eps >= 0.0) || !(floor >= 0.0) || !std::isfinite(eps) || !std::isfinite(floor)) return PINN_ERR_SIZE;
+    if (!binned || !w_out || !cdf_out) return PINN_ERR_NULL;
+    return causal::launch_cdf(causal::CdfArgs{binned, n_bins, eps, floor, w_out, cdf_out}, static_cast<hipStream_t>(stream));
+}
+
+int pinn_sample_box_cdf(uint64_t seed, uint32_t stream_id, uint64_t first, int64_t n, int dim, const double lo[4], const double hi[4],
+                        const float* t_cdf, int n_bins, float* x, float* y, float* z, float* t, void* stream) {
+    if (bad_bins(n, n_bins)) return PINN_ERR_SIZE;
+    if (dim != 3 && dim != 4) return PINN_ERR_LAYERS;
+    if (!lo || !hi || !t_cdf || (n > 0 && (!x || !y || !t || (dim == 4 && !z)))) return PINN_ERR_NULL;
+    if (n == 0) return PINN_OK;
+    float* const cols[4] = {x, y, dim == 4 ? z : t, dim == 4 ? t : nullptr};
+    return causal::launch_box_cdf(sample::box_args(seed, stream_id, first, (uint32_t)n, dim, lo, hi, cols), t_cdf, n_bins,
+                                  static_cast<hipStream_t>(stream));
 }
 
 int pinn_net_streams(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,

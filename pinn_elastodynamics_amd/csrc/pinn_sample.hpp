@@ -70,8 +70,9 @@ __global__ __launch_bounds__(THREADS) void box_kernel(const BoxArgs a) {
     }
 }
 
-inline int launch_box(uint64_t seed, uint32_t stream_id, uint64_t first, uint32_t n, int dim, const double* lo, const double* hi,
-                      float* const* cols, hipStream_t st) {
+// the arguments of a box draw (pinn_causal.hpp draws with them too)
+inline BoxArgs box_args(uint64_t seed, uint32_t stream_id, uint64_t first, uint32_t n, int dim, const double* lo, const double* hi,
+                        float* const* cols) {
     BoxArgs a;
     a.seed = seed;
     a.first = first;
@@ -85,6 +86,12 @@ inline int launch_box(uint64_t seed, uint32_t stream_id, uint64_t first, uint32_
         a.hi[k] = on ? (float)hi[k] : 0.f;
         a.out[k] = on ? cols[k] : nullptr;
     }
+    return a;
+}
+
+inline int launch_box(uint64_t seed, uint32_t stream_id, uint64_t first, uint32_t n, int dim, const double* lo, const double* hi,
+                      float* const* cols, hipStream_t st) {
+    const BoxArgs a = box_args(seed, stream_id, first, n, dim, lo, hi, cols);
     const uint32_t blocks = (n + THREADS - 1) / THREADS;
     if (dim == 3) hipLaunchKernelGGL((box_kernel<3>), dim3(blocks), dim3(THREADS), 0, st, a);
     else hipLaunchKernelGGL((box_kernel<4>), dim3(blocks), dim3(THREADS), 0, st, a);

@@ -20,6 +20,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import causal as causal_sampling
 from . import material
 from .model_base import ShardedSetsModel
 from .net_api import write_checkpoint
@@ -146,7 +147,8 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
         xs = self._device_columns((x, y, t))
         return self._score_device(xs, self._score_weights(weights)).detach().cpu().numpy().reshape(-1, 1)
 
-    def refine_collocation(self, candidates, n_replace, weights=None, *, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
+    def refine_collocation(self, candidates, n_replace, weights=None, *, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=(),
+                           causal=False):
         """Residual-adaptive refinement that keeps the set's size: score this rank's rows of the collocation set and the ``candidates``
         [Nc,3] (x, y, t) on the device, take the K = min(n_replace, Nc, rows) highest-scoring candidates and the K lowest-scoring rows
         (engine.select_k), pair them (pair_replacements: highest candidate against lowest row) and overwrite row j with candidate j only
@@ -165,9 +167,38 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
         [replaced, 3]; ``candidate_indices`` are sample indices of the draw.  An array, select="top" and no exclude: exactly the calls above.
         Returns dict(replaced, rows, candidate_indices, score_replaced_max, score_inserted_min): how many rows changed, their row numbers in the
         whole set and the candidates that took their places (pairing order), the largest score that left and the smallest that came in (None
-        when nothing was replaced).  Synchronises once (the indices come to the host)."""
-        C = Candidates(self, candidates, 3, "(x, y, t)", select, power, c, seed, stream, box, exclude)
+        when nothing was replaced).  Synchronises once (the indices come to the host).
+        ``causal=True`` (int candidates only): the candidates' time column is drawn from the model's current causal table (resample_collocation,
+        train(causal=...)) over the box's time range instead of the uniform law, so refinement and causal sampling compose instead of refinement
+        pulling rows back to late times; without a table ValueError."""
+        C = Candidates(self, candidates, 3, "(x, y, t)", select, power, c, seed, stream, box, exclude, causal)
         return refine_sharded_set(self, C, n_replace, self._score_weights(weights), ("x_c", "y_c", "t_c"))
+
+    # ------------------------------------------------------------------------------------------
+    # causal sampling of the collocation set's time coordinate (causal.py)
+    # ------------------------------------------------------------------------------------------
+    def residual_profile(self, bins, candidates, weights=None, *, exclude=(), seed=None):
+        """(profile, counts), numpy [bins] each: the mean of residual_score per time bin of (lb_t, ub_t) over ``candidates`` probe points drawn
+        uniformly in (lb, ub) on the device, and how many of them each bin holds; points inside the ``exclude`` discs (xc, yc, r) count in
+        neither.  Four device calls (sample_box, residual_score, refine_keys in mask mode, binned_sums) and one download of 2 * bins doubles.
+        The probe points are the same on every rank (stream 0x80000000 | round, ``round`` this model's count of device-drawn rounds), so with
+        the same parameters every rank gets the same numbers bit for bit, no collective.  ``weights`` are the score's term weights, as in
+        residual_score.  The causal weights and the table of a profile are not returned here: resample_collocation makes them from the same
+        four calls plus causal_cdf and returns them as ``w`` and ``cdf``."""
+        return causal_sampling.residual_profile(self, bins, candidates, weights, exclude=exclude, seed=seed)
+
+    def resample_collocation(self, causal):
+        """Causal sampling (Wang, Sankaran, Perdikaris): THIS RANK'S rows of the collocation set are drawn again with the time coordinate's
+        density ~ max(w, floor), w_b = exp(-eps / ref * sum of the mean scores of the earlier time bins), the profile taken as in
+        residual_profile.  ``causal``: dict(bins, eps, candidates, floor=0.0, exclude=(), seed=None, ref="first", weights=None, slack=None).
+        ``ref="first"``: the mean score over the probe points of this model's FIRST profile (fetched once per model), which makes ``eps``
+        dimensionless; a float is used as that scale.  The rows: N_shard + ``slack`` (default N_shard / 8 + 64) points from
+        engine.sample_box(t_cdf=table) on the stream round * world + rank, the first N_shard of them outside the ``exclude`` discs go in; where
+        fewer are valid the remaining rows keep their old points (no loop, no fallback draw).  N, the 1/N weights, the block boundaries and the
+        shards stay; the host copies follow as in refine_collocation.  The device table stays as ``self._causal_cdf`` (refine_collocation(causal=True)
+        draws from it).  Returns dict(redrawn, kept, w, cdf, profile, counts): rows drawn again and rows kept, the weights [bins], the table
+        [bins + 1], the profile and the counts [bins] (numpy, downloaded here only -- train(causal=...) leaves them on the device)."""
+        return causal_sampling.resample_collocation(self, causal, ("x_c", "y_c", "t_c"))
 
     # ------------------------------------------------------------------------------------------
     # identification of E, mu, rho: the moment sums of the collocation residuals (material.py)
@@ -272,7 +303,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
     # ------------------------------------------------------------------------------------------
     # training drivers
     # ------------------------------------------------------------------------------------------
-    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None, identify=None):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None, identify=None, causal=None):
         """Adam loop of INF:282-319: contiguous collocation blocks, ``iter`` steps per block, all
         side sets fed whole to every block.  Returns the per-step lists
         (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss).  ``record="pre"`` (default): each recorded value is the loss
@@ -289,10 +320,21 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
         constants; the next step's call sees them.  (step, E, mu, rho) is appended to ``self.material_rec``.  Cost: one more forward pass
         over the block per identified step -- measured on an MI355X at 8x64, f16x3, 2 M points: 4.61 ms per step with None, 7.09 ms with
         every=1, 5.24 ms with every=4 (profiles/material_sums_calls.txt); choose ``every`` accordingly.  With None the loop makes exactly the
-        calls it makes without the keyword."""
+        calls it makes without the keyword.
+        ``causal``: None, or dict(every, bins, eps, candidates, floor=0.0, exclude=(), seed=None, ref="first") -- resample_collocation's entries
+        plus ``every``: behind every ``every``-th step of this call, in front of refinement's hook, the time profile of the residual score is
+        taken on the device and this rank's rows are drawn again from its causal table (causal.CausalSchedule).  Every trigger redraws, the
+        first one of a fresh model too: with ``ref="first"`` and no scale yet it fetches its own profile (2 * bins doubles, once per model)
+        and takes the scale from it.  Otherwise the profile, the weights and the table stay on the device.  Each trigger is ONE HOST
+        SYNCHRONISATION, as a refinement round is: the count of valid drawn points and the redrawn rows (N_shard points, 12 bytes each) come
+        to the host for the host copies of the set, and the float64 columns are rewritten (26 - 49 ms per trigger at 2 M rows); choose
+        ``every`` so that this is small beside ``every`` steps.  Measured on an MI355X at 8x64, f16x3, 2 M points: 4.45 - 4.48 ms per step
+        with None (the code before the keyword: 4.46 - 4.49), 4.78 - 4.93 ms with every=100, 65 536 probe points and the default scale
+        (4.74 - 4.83 with a given one; profiles/causal_calls.txt).  With None the loop makes exactly the calls it makes without the keyword."""
         if record not in ("pre", "post"):
             raise ValueError("record must be 'pre' or 'post'")
         sched, vsched, msched, step = schedule(self, refine), validate_schedule(self, validate), material.schedule(self, identify), 0
+        csched = causal_sampling.schedule(self, causal, ("x_c", "y_c", "t_c"))
         loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss = [], [], [], [], []
         P = self.n_params
         col_num = self._n_collo
@@ -323,10 +365,12 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
                 if self.verbose and it % 10 == 0 and self.rank == 0:
                     tm = self._terms_from_sums(rec[it].detach().cpu().numpy().reshape(len(_SLOTS), 8), idx_end - idx_start)
                     print('It: %d, Loss: %.3e' % (it, tm["loss"]))
-                if sched is not None or vsched is not None or msched is not None:
+                if sched is not None or vsched is not None or msched is not None or csched is not None:
                     step += 1
                     if msched is not None:
                         msched.after_step()
+                    if csched is not None:
+                        csched.after_step(step)
                     if sched is not None:
                         sched.after_step(step)
                     if vsched is not None:
@@ -433,9 +477,9 @@ class DeepHPMConfined(DeepHPM):
             if layers is not None:
                 self._aux_nets[name] = self.load_NN(path, layers) if path else xavier_init(layers, np.random.default_rng(seed + off))
 
-    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None, identify=None):
+    def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None, identify=None, causal=None):
         """CONF:373-408 returns three lists: (loss_f_uv, loss_f_s, loss)."""
-        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record, refine, validate, identify)
+        loss_f_uv, loss_f_s, _, _, loss = super().train(iter, learning_rate, batch_num, record, refine, validate, identify, causal)
         return loss_f_uv, loss_f_s, loss
 
     def save_NN(self, fileDir, TYPE=''):

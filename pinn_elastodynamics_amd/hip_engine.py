@@ -10,7 +10,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .capi import DEFAULT_LIB, FLAG_STATE_FP16, FLAG_TWO_KERNEL, FLAG_WEIGHTS_PACKED, MATERIAL_SUMS, MATERIAL_SUMS_NC3D, MATERIAL_SUMS_PLATE, PREC, PinnLib, PinnLibError, adjoint_shift
+from .capi import DEFAULT_LIB, FLAG_STATE_FP16, FLAG_TWO_KERNEL, FLAG_WEIGHTS_PACKED, MATERIAL_SUMS, MATERIAL_SUMS_NC3D, MATERIAL_SUMS_PLATE, MAX_TIME_BINS, PREC, PinnLib, PinnLibError, adjoint_shift
 
 
 def param_count(layers: Sequence[int]) -> int:
@@ -404,13 +404,45 @@ class HipEngine(LbfgsMixin):
         self.lib.select_k(score.data_ptr(), score.numel(), k, largest, out.data_ptr(), ws, ws_bytes, self._stream())
         return out
 
-    def sample_box(self, n: int, lo, hi, seed: int, stream: int = 0, first: int = 0):
+    def sample_box(self, n: int, lo, hi, seed: int, stream: int = 0, first: int = 0, t_cdf: Optional[torch.Tensor] = None):
         """n points uniform in the box [lo, hi] (3 bounds: columns x, y, t; 4: x, y, z, t) as a tuple of device columns (pinn_sample_box):
-        Philox4x32-10 keyed by ``seed``, point i a function of (seed, stream, first + i) alone.  No synchronisation."""
+        Philox4x32-10 keyed by ``seed``, point i a function of (seed, stream, first + i) alone.  No synchronisation.
+        ``t_cdf``: a device float32 [bins + 1] table (causal_cdf) -- the time column then follows its piecewise-constant density over the bins
+        of [lo_t, hi_t] (pinn_sample_box_cdf), the space columns keep their bits.  None: exactly the call above."""
         dim = len(lo)
         cols = tuple(torch.empty(int(n), dtype=torch.float32, device=self.device) for _ in range(dim))
-        self.lib.sample_box(seed, stream, first, n, lo, hi, [c.data_ptr() for c in cols], self._stream())
+        if t_cdf is None:
+            self.lib.sample_box(seed, stream, first, n, lo, hi, [c.data_ptr() for c in cols], self._stream())
+        else:
+            self._chk(t_cdf)
+            self.lib.sample_box(seed, stream, first, n, lo, hi, [c.data_ptr() for c in cols], self._stream(), t_cdf.data_ptr(), t_cdf.numel() - 1)
         return cols
+
+    # ---- causal sampling: per-time-bin score sums, the causal weights and their CDF ---------------------------------
+    def binned_sums(self, value, coord, lo: float, hi: float, n_bins: int, out: Optional[torch.Tensor] = None):
+        """Per-bin sums of the device tensor ``value`` over ``n_bins`` equal bins of [lo, hi] of the device tensor ``coord``
+        (pinn_binned_sums): the device float64 tensor [2, n_bins] = the sums, then the counts; a value that is negative or not finite (the
+        -inf keys of refine_keys' mask mode) is skipped.  fp64, fixed order, no synchronisation."""
+        self._chk(value)
+        self._chk(coord, value.numel())
+        # (the size depends on the bin count only: one buffer for the 64 bins a call may have)
+        ws, ws_bytes = self._scratch("_bins_ws", lambda: self.lib.binned_sums_workspace_bytes(0, MAX_TIME_BINS))
+        if out is None:
+            out = torch.empty((2, int(n_bins)), dtype=torch.float64, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 2 * int(n_bins)
+        self.lib.binned_sums(value.data_ptr(), coord.data_ptr(), value.numel(), lo, hi, n_bins, out.data_ptr(), ws, ws_bytes, self._stream())
+        return out
+
+    def causal_cdf(self, binned, eps: float, floor: float = 0.0):
+        """(w, cdf) of pinn_causal_cdf from the [2, bins] output of binned_sums: the device float64 tensor [bins] of the causal weights
+        w_b = exp(-eps * sum of the earlier bins' mean values) and the device float32 tensor [bins + 1] of the CDF of max(w, floor) that
+        sample_box(t_cdf=...) reads.  One small launch, no synchronisation."""
+        assert binned.is_cuda and binned.dtype == torch.float64 and binned.is_contiguous() and binned.dim() == 2 and binned.shape[0] == 2
+        n_bins = int(binned.shape[1])
+        w = torch.empty(n_bins, dtype=torch.float64, device=self.device)
+        cdf = torch.empty(n_bins + 1, dtype=torch.float32, device=self.device)
+        self.lib.causal_cdf(binned.data_ptr(), n_bins, eps, floor, w.data_ptr(), cdf.data_ptr(), self._stream())
+        return w, cdf
 
     def refine_keys(self, score, cols, balls=(), mode: str = "mask", power: float = 1.0, c: float = 1.0, seed: int = 0, stream: int = 0, first: int = 0):
         """Selection keys of the device scores ``score`` at the device columns ``cols`` (x, y, t) or (x, y, z, t) (pinn_refine_keys): -inf

@@ -79,11 +79,16 @@ class Candidates:
     """The candidates of one refine_collocation call.  ``candidates``: a float64 [Nc, ncols] array (converted and uploaded by ``columns``) or an
     int: that many points drawn on the device in ``box`` = (lo, hi) -- default the model's (lb, ub) -- by engine.sample_box(seed, stream), the
     stream by default  round * world + rank  with ``round`` the model's count of device-drawn refinements so far.  ``plain``: an array, greedy
-    selection, nothing excluded -- the path that existed before keys did, which makes the engine calls it always made."""
+    selection, nothing excluded -- the path that existed before keys did, which makes the engine calls it always made.  ``causal``: the drawn
+    points' time column follows the model's current causal table (model._causal_cdf, causal.py) over the box's time range instead of the
+    uniform law; without a table, or with an array, ValueError."""
 
-    def __init__(self, model, candidates, ncols, names, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=()):
+    def __init__(self, model, candidates, ncols, names, select="top", power=1.0, c=1.0, seed=None, stream=None, box=None, exclude=(), causal=False):
         if select not in ("top", "sample"):
             raise ValueError("select must be 'top' or 'sample'")
+        self.t_cdf = getattr(model, "_causal_cdf", None) if causal else None
+        if causal and (self.t_cdf is None or not (isinstance(candidates, (int, np.integer)) and not isinstance(candidates, bool))):
+            raise ValueError("causal=True needs an int number of candidates and a table: call resample_collocation(causal=...) or train(causal=...) first")
         self.select, self.power, self.c = select, float(power), float(c)
         self.exclude = [tuple(float(v) for v in b) for b in exclude]
         for b in self.exclude:
@@ -111,6 +116,8 @@ class Candidates:
 
     def columns(self, engine, device):
         """the candidates as device columns"""
+        if self.drawn and self.t_cdf is not None:
+            return engine.sample_box(self.n, self.lo, self.hi, self.seed, self.stream, t_cdf=self.t_cdf)
         if self.drawn:
             return engine.sample_box(self.n, self.lo, self.hi, self.seed, self.stream)
         return device_columns(self.C, device)
@@ -162,6 +169,27 @@ def update_host_columns(model, names, r_host, c_host, C):
         getattr(model, nm)[r_host, 0] = C[c_host, k]
 
 
+def overwrite_rows(model, names, s0, ri, cand, ci, inserted):
+    """Rows ``s0 + ri`` of the sharded set (``s0``: the first row of this rank's shard; ``ri``, ``ci`` device index tensors of one length) take
+    the points ``cand[k][ci]`` of the device columns ``cand``: the device set (_collo_full), the host columns ``names`` and _collo_host
+    follow, the shard cache is dropped.  ``inserted(cand, ci, c_host)`` gives the points as a host [m, len(names)] float64 array.  One
+    download (the indices, and the points where only the device has them).  Returns (rows, candidate indices, points) on the host, or None
+    where nothing moves.  Shared by refinement (below) and the causal redraw (causal.py)."""
+    m = int(ri.numel())
+    model._collo_cache = {}
+    if m == 0:
+        return None
+    if model._collo_full is not None:
+        for k in range(len(names)):
+            model._collo_full[k][s0 + ri] = cand[k][ci]
+    r_host, c_host = ri.cpu().numpy() + s0, ci.cpu().numpy()
+    pts = inserted(cand, ci, c_host)
+    update_host_columns(model, names, r_host, np.arange(m), pts)
+    for k in range(len(names)):
+        model._collo_host[k][r_host] = pts[:, k].astype(np.float32)
+    return r_host, c_host, pts
+
+
 def refine_sharded_set(model, C, n_replace, w, names):
     """refine_collocation of the classes that keep the set as host columns plus device shards (_collo_host / _collo_full / _collo_cache, _rows,
     _shard, _n_collo) and score through ``model._score_device(columns, weights, packed=...)``.  ``C``: a Candidates, or candidates
@@ -180,19 +208,11 @@ def refine_sharded_set(model, C, n_replace, w, names):
     s_rows = model._score_device(rows, w)
     s_cand = model._score_device(cand, w, packed=True)
     ri, ci, rs, cs = select_pairs(model.engine, s_rows, s_cand, K, C.keys(model.engine, s_cand, cand))
-    m = int(ri.numel())
-    model._collo_cache = {}
-    if m == 0:
+    moved = overwrite_rows(model, names, s0, ri, cand, ci, C.inserted)
+    if moved is None:
         return out
-    if model._collo_full is not None:
-        for k in range(len(names)):
-            model._collo_full[k][s0 + ri] = cand[k][ci]
-    r_host, c_host = ri.cpu().numpy() + s0, ci.cpu().numpy()
-    pts = C.inserted(cand, ci, c_host)
-    update_host_columns(model, names, r_host, np.arange(m), pts)
-    for k in range(len(names)):
-        model._collo_host[k][r_host] = pts[:, k].astype(np.float32)
-    out.update(replaced=m, rows=r_host, candidate_indices=c_host, score_replaced_max=float(rs.max()), score_inserted_min=float(cs.min()))
+    r_host, c_host, pts = moved
+    out.update(replaced=len(r_host), rows=r_host, candidate_indices=c_host, score_replaced_max=float(rs.max()), score_inserted_min=float(cs.min()))
     if not C.plain:
         out["candidates"] = pts
     return out
