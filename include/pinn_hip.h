@@ -642,6 +642,57 @@ int pinn_plate2d_step(float* params_flat, const int* layers, int n_layers,
                       float* grad_flat_out, int accumulate, const pinn_adam_state* adam,
                       int precision_mode, void* workspace, size_t ws_bytes, void* stream);
 
+/* A traction boundary set of the wave family: the traction vector of net_surf_var (INF:267-276: s11 nx + s12 ny, s12 nx + s22 ny) on the
+ * net's own stress outputs (u, v, ut, vt, s11, s22, s12; value stream only) with PER-POINT normals and PER-POINT targets -- a traction-free
+ * cavity or inclined / curved free surface (targets 0), a prescribed time-dependent load (targets = the load) -- and its gradient:
+ *   normals_and_tractions   DEVICE, SoA [4][n] = nx, ny, tx, ty at the set's points (traction-free: rows 2 and 3 zero)
+ *   r_x = s11 nx + s12 ny - tx,   r_y = s12 nx + s22 ny - ty
+ *   loss_terms_out = (sum r_x^2, sum r_y^2)      grad_flat_out (+)= d/dparams (weights[0] sum r_x^2 + weights[1] sum r_y^2)
+ * The normals are used AS GIVEN: they are not normalised, so a caller may fold quadrature weights (arc length x time step) into them.
+ * One stream through the net: the paths, workspace rule, flags and precision modes are pinn_data_loss_grad's (every 16-bit mode and
+ * PINN_PREC_FP32; pinn_path_for(.., PINN_HEAD_DATA, ..) answers for it; one path count per call); for the nets the one-stream fused kernel
+ * covers it runs there as set kind 2.  layers must end in 7 outputs (PINN_ERR_LAYERS); normals_and_tractions == NULL with n > 0 is
+ * PINN_ERR_NULL; n == 0 writes zero sums and leaves the gradient as `accumulate` says.
+ * Precision: the chain is the data head's, only the adjoint seed differs (three of seven outputs, two products each).  Measured against the
+ * float64 oracle (profiles/wave_traction_calls.txt) its error is the data head's at the same net and points: sums 1e-7, gradient 6e-6 at
+ * 16 385 points of the 8 x 64 net in PINN_PREC_F16X3, 2.6e-5 at 1000, 2.1e-4 at ONE point (both heads alike: the narrow one-stream kernel
+ * hands its states to the weight gradient as fp16 high parts), 1.3e-7 at 8 x 80.  At the trained fixture weights_wave64.npz the error
+ * falls with n as the data head's does (9e-5 at 1000 points, 1.6e-5 at 256 000): NO N-dependent bias of the kind the plate's traction
+ * head carries was found. */
+int pinn_wave2d_traction_loss_grad(const float* params_flat, const int* layers, int n_layers,
+                                   const float* x, const float* y, const float* t, int64_t n,
+                                   const double lb[3], const double ub[3], int normalize,
+                                   const float* normals_and_tractions, const float weights[2],
+                                   float* loss_terms_out, float* grad_flat_out, int accumulate,
+                                   int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
+/* pinn_wave2d_step with a traction set (INF:267-276, pinn_wave2d_traction_loss_grad's arguments as trac_*).  The value-only sets and the
+ * traction set form ONE set table -- the one-stream part of the step's persistent launch, the traction set as set kind 2 behind the
+ * value-only sets --, so n_sets <= PINN_MAX_SETS - 1 here (PINN_ERR_SIZE), all of the table's weights are normalised by ONE maximum, and the
+ * step stays  weight repack | ONE persistent launch for all point sets | ONE reduction (+ Adam).
+ * The fall-back rule and the same-bits guarantee are pinn_wave2d_step's: where the one launch does not apply -- other widths / depths,
+ * PINN_PREC_FP32, an empty collocation batch, a workspace without room for both parts, pinn_debug_set_step_launch(0) -- the entry point
+ * makes the separate calls inside: pinn_wave2d_loss_grad, then the same set table as one multi-set call into the same gradient, then
+ * pinn_adam_step when adam != NULL.  The RESULTS are the same bits either way.  (They are NOT the bits of pinn_wave2d_step followed by
+ * pinn_wave2d_traction_loss_grad: a set table has one weight normalisation and its sets share the workgroups' partial sums; the two agree
+ * to the mode's accuracy.)
+ * trac_loss_terms_out receives the two sums.  trac_n == 0 (trac_* pointers may then be NULL): exactly pinn_wave2d_step's calls, Adam fold
+ * included; trac_loss_terms_out, if given, reports zeros.  trac_n > 0 needs every trac_* pointer (PINN_ERR_NULL); trac_n < 0 is
+ * PINN_ERR_SIZE.  The arguments -- pointers, sizes, the layer list, the precision word, the collocation call's workspace -- are checked
+ * before anything is written; with an EMPTY collocation batch (n == 0) a workspace too small for the sets' own plan is reported by the
+ * multi-set call, after the collocation sums were zeroed.
+ * Cost: profiles/wave_traction_calls.txt, section 3. */
+int pinn_wave2d_step_traction(float* params_flat, const int* layers, int n_layers,
+                              const float* x, const float* y, const float* t, int64_t n,
+                              const double lb[3], const double ub[3], int normalize,
+                              double E, double mu, double rho, int plane_strain,
+                              const float term_weights[7], float* loss_terms_out,
+                              const pinn_point_set* sets, int n_sets,
+                              const float* trac_x, const float* trac_y, const float* trac_t, int64_t trac_n,
+                              const float* trac_normals_and_tractions, const float trac_weights[2], float* trac_loss_terms_out,
+                              float* grad_flat_out, int accumulate, const pinn_adam_state* adam,
+                              int precision_mode, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- 3-D Navier-Cauchy extension (BASELINE.json configs[4]).  NOT in the reference: all four reference scripts are 2-D + time
  * (SURVEY.md section 0), so these entry points have no reference lines to replace; they state the 3-D form of net_f_sig
  * (INF:221-265) the way oracle/nc3d_oracle.py spells it out, and parity for them is unpinned by definition.
@@ -835,6 +886,10 @@ int pinn_p2p_debug_force_coarse(int enable);
  * fused kernel applies; 1 (default) prefers the fused kernel.  Returns the previous setting.  Both paths
  * compute the same numbers to the precision mode's accuracy (tests/test_gpu_parity.py). */
 int pinn_debug_set_fused(int enable);
+/* Testing hook (process-wide): 0 makes the step entry points (pinn_wave2d_step, pinn_wave2d_step_traction, pinn_plate2d_step) take their
+ * fall-back -- the separate calls inside -- even where the one launch applies; 1 (default) prefers the one launch.  Returns the previous
+ * setting.  The results are the same bits either way, which is what the tests hold with it. */
+int pinn_debug_set_step_launch(int enable);
 /* Tuning hook (process-wide): the XCD-aware step assignment of the fused collocation kernels.  Workgroups are dispatched round-robin over the 8
  * XCDs and the odd XCDs of an MI355X run these kernels 2-3 % slower than the even ones (profiles/r05_workgroup_lifetimes.txt), so the even-XCD
  * workgroups take `permille` / 1000 more steps (as the tail of the launch; default 16).  0 turns it off; returns the previous setting.  The

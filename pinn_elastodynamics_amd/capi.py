@@ -166,6 +166,8 @@ PROTOTYPES = {
     "pinn_data_loss_grad_multi": (_i32, _NET + [C.POINTER(PointSet), _i32] + _BOX + [_vp, _i32] + _TAIL),
     "pinn_wave2d_step": (_i32, _NET + _PTS3 + _WAVE + [_vp, C.POINTER(PointSet), _i32, _vp, _i32, _ADAM] + _TAIL),
     "pinn_plate2d_step": (_i32, _NET + _PTS3 + [_vp] + _MAT + [_pf32, _vp, _vp, _vp, _vp, _i64, _vp, _pf32, _vp, _vp, _i32, _ADAM] + _TAIL),
+    "pinn_wave2d_traction_loss_grad": (_i32, _NET + _PTS3 + [_vp, _pf32] + _OUT + _TAIL),
+    "pinn_wave2d_step_traction": (_i32, _NET + _PTS3 + _WAVE + [_vp, C.POINTER(PointSet), _i32, _vp, _vp, _vp, _i64, _vp, _pf32, _vp, _vp, _i32, _ADAM] + _TAIL),
     "pinn_nc3d_loss_grad": (_i32, _NET + _PTS4 + _MAT + [_pf32] + _OUT + _TAIL),
     "pinn_nc3d_data_loss_grad": (_i32, _NET + _PTS4 + [_vp, _pf32] + _OUT + _TAIL),
     "pinn_nc3d_fields": (_i32, _NET + _PTS4 + [_vp] + _TAIL),
@@ -187,6 +189,7 @@ PROTOTYPES = {
     "pinn_p2p_destroy": (_i32, [_vp]),
     "pinn_p2p_debug_force_coarse": (_i32, [_i32]),
     "pinn_debug_set_fused": (_i32, [_i32]),
+    "pinn_debug_set_step_launch": (_i32, [_i32]),
     "pinn_debug_set_xcd_bonus": (_i32, [_i32]),
     "pinn_debug_set_fused_grid_cap": (_i32, [_i32]),
     "pinn_debug_cache_policy": (_i32, [_pi32, _i32, _i32, _psz, _psz]),
@@ -360,6 +363,10 @@ class PinnLib:
         """0: two-kernel path, 1: fused kernel where it applies (default)"""
         return int(self.lib.pinn_debug_set_fused(int(bool(enable))))
 
+    def set_step_launch(self, enable) -> int:
+        """0: the step entry points make their separate calls inside, 1: the one launch where it applies (default)"""
+        return int(self.lib.pinn_debug_set_step_launch(int(bool(enable))))
+
     def fused_weight_limit(self) -> float:
         return float(self.lib.pinn_fused_weight_limit())
 
@@ -421,6 +428,20 @@ class PinnLib:
         """pinn_plate2d_step.  adam: None or (m, v, lr, beta1, beta2, eps, step)."""
         self.call("pinn_plate2d_step", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), frozen, float(E), float(mu), float(rho),
                   self._floats(term_weights, 5), loss_out, hx, hy, ht, int(hn), haux, self._floats(hweights, 2), hloss_out, grad_out,
+                  int(bool(accumulate)), self.adam_state(adam), *self._tail(prec, ws, ws_bytes, stream))
+
+    def wave2d_traction_loss_grad(self, params, layers, x, y, t, n, lb, ub, normalize, aux, weights, loss_out, grad_out, accumulate,
+                                  prec, ws, ws_bytes, stream=0):
+        """pinn_wave2d_traction_loss_grad.  aux: device [4][n] = nx, ny, tx, ty; loss_out: 2 floats (sum r_x^2, sum r_y^2)"""
+        self.call("pinn_wave2d_traction_loss_grad", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize), aux, self._floats(weights, 2),
+                  loss_out, grad_out, int(bool(accumulate)), *self._tail(prec, ws, ws_bytes, stream))
+
+    def wave2d_step_traction(self, params, layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, loss_out, sets, tx, ty, tt, tn,
+                             taux, tweights, tloss_out, grad_out, accumulate, adam, prec, ws, ws_bytes, stream=0):
+        """pinn_wave2d_step_traction.  sets / adam: as wave2d_step; (tx, ty, tt, tn, taux, tweights, tloss_out): the traction set."""
+        self.call("pinn_wave2d_step_traction", *self._net_points(params, layers, (x, y, t), n, lb, ub, normalize),
+                  *self._wave_head(E, mu, rho, plane_strain, term_weights), loss_out, self._set_array(PointSet, sets), len(sets),
+                  tx or None, ty or None, tt or None, int(tn), taux or None, self._floats(tweights, 2), tloss_out or None, grad_out,
                   int(bool(accumulate)), self.adam_state(adam), *self._tail(prec, ws, ws_bytes, stream))
 
     def wave2d_fields(self, params, layers, x, y, t, n, lb, ub, normalize, fields_out, prec, ws, ws_bytes, stream=0):

@@ -80,6 +80,7 @@ static void input_map(const double* lb, const double* ub, int normalize, Call& c
 using namespace pinn;
 
 static int g_use_fused = 1;
+static int g_step_launch = 1;      // pinn_debug_set_step_launch: 0 = the step entry points make their separate calls inside
 static unsigned long long* g_dbg_stamps = nullptr;
 static float* g_prof_ms = nullptr;
 static ProfRing g_ring;
@@ -186,6 +187,12 @@ int pinn_debug_cache_policy(const int* layers, int n_layers, int head, size_t* i
 }
 
 int pinn_debug_set_fused_grid_cap(int cap) { const int old = g_fused_grid_cap; g_fused_grid_cap = cap < 0 ? 0 : cap; return old; }
+
+int pinn_debug_set_step_launch(int enable) {
+    const int old = g_step_launch;
+    g_step_launch = enable ? 1 : 0;
+    return old;
+}
 
 int pinn_debug_set_fused(int enable) {
     const int old = g_use_fused;
@@ -613,7 +620,7 @@ int pinn_wave2d_step(float* params_flat, const int* layers, int n_layers, const 
     int64_t side_total = 0;
     for (int k = 0; k < n_sets; ++k) side_total += sets[k].n;
     // ---- the one-launch form: collocation set and side sets through fused_step_kernel, one reduction (+ Adam) behind it
-    if (n > 0 && side_total > 0 && term_weights && loss_terms_out && grad_flat_out) {
+    if (n > 0 && side_total > 0 && term_weights && loss_terms_out && grad_flat_out && g_step_launch) {
         Call c;
         const Impl* impl = nullptr;
         rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
@@ -643,6 +650,97 @@ int pinn_wave2d_step(float* params_flat, const int* layers, int n_layers, const 
                                        ws_bytes, stream);
         if (rc) return rc;
     }
+    return adam_tail(params_flat, layers, n_layers, grad_flat_out, adam, stream);
+}
+
+int pinn_wave2d_traction_loss_grad(const float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t,
+                                   int64_t n, const double lb[3], const double ub[3], int normalize, const float* normals_and_tractions,
+                                   const float weights[2], float* loss_terms_out, float* grad_flat_out, int accumulate, int precision_mode,
+                                   void* workspace, size_t ws_bytes, void* stream) {
+    Own o;
+    o.weights = weights;
+    o.aux = normals_and_tractions;
+    o.loss_grad(loss_terms_out, grad_flat_out, accumulate);
+    return point_call(CALL_WAVE_TRACTION_LOSS_GRAD, params_flat, layers, n_layers, x, y, nullptr, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, o);
+}
+
+int pinn_wave2d_step_traction(float* params_flat, const int* layers, int n_layers, const float* x, const float* y, const float* t, int64_t n,
+                              const double lb[3], const double ub[3], int normalize, double E, double mu, double rho, int plane_strain,
+                              const float term_weights[7], float* loss_terms_out, const pinn_point_set* sets, int n_sets, const float* trac_x,
+                              const float* trac_y, const float* trac_t, int64_t trac_n, const float* trac_normals_and_tractions,
+                              const float trac_weights[2], float* trac_loss_terms_out, float* grad_flat_out, int accumulate,
+                              const pinn_adam_state* adam, int precision_mode, void* workspace, size_t ws_bytes, void* stream) {
+    if (trac_n < 0) return PINN_ERR_SIZE;
+    if (trac_n > 0 && (!trac_x || !trac_y || !trac_t || !trac_normals_and_tractions || !trac_weights || !trac_loss_terms_out)) return PINN_ERR_NULL;
+    if (trac_n == 0) {      // no traction points: pinn_wave2d_step's calls, its Adam fold included
+        const int rc = pinn_wave2d_step(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, loss_terms_out,
+                                        sets, n_sets, grad_flat_out, accumulate, adam, precision_mode, workspace, ws_bytes, stream);
+        if (rc || !trac_loss_terms_out) return rc;
+        return (int)hipMemsetAsync(trac_loss_terms_out, 0, 2 * sizeof(float), static_cast<hipStream_t>(stream));
+    }
+    // the value-only sets and the traction set form ONE set table (the one-stream part of the step launch): one slot is the traction set's
+    if (n_sets < 0 || n_sets > PINN_MAX_SETS - 1) return PINN_ERR_SIZE;
+    if (n_sets > 0 && !sets) return PINN_ERR_NULL;
+    int rc = check_adam(adam);
+    if (!rc) rc = check_point_sets(sets, n_sets);
+    if (rc) return rc;
+    // every argument is checked before anything is written: the collocation call's here, not behind the first launch
+    Call c;
+    const Impl* impl = nullptr;
+    rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);
+    if (rc) return rc;
+    if (!term_weights || !loss_terms_out || !grad_flat_out) return PINN_ERR_NULL;
+    if (c.net.nout != 7) return PINN_ERR_LAYERS;
+    set_hooke(c, E, mu, rho, plane_strain);
+    for (int i = 0; i < 7; ++i) c.tw[i] = term_weights[i];
+    c.loss_out = loss_terms_out;
+    c.grad_out = grad_flat_out;
+    c.accumulate = accumulate;
+    // d: the one-stream sets of the step as ONE multi-set call -- pinn_data_loss_grad_multi's table with the traction set (kind 2) behind the
+    // value-only sets, under one weight normalisation
+    Call d = c;
+    for (int i = 0; i < 16; ++i) d.tw[i] = 0.0f;
+    d.loss_out = nullptr;
+    copy_point_sets(sets, n_sets, d);
+    DataSet& T = d.sets[n_sets];
+    T = DataSet{};
+    T.x = trac_x;
+    T.y = trac_y;
+    T.t = trac_t;
+    T.targets = nullptr;
+    T.n = (long)trac_n;
+    for (int i = 0; i < 16; ++i) T.tw[i] = 0.0f;
+    T.tw[0] = trac_weights[0];
+    T.tw[1] = trac_weights[1];
+    T.loss_out = trac_loss_terms_out;
+    T.head = 2;
+    T.aux = trac_normals_and_tractions;
+    d.nsets = n_sets + 1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // ---- the one-launch form: collocation set, then the one-stream part with all of d's sets, one reduction (+ Adam)
+    if (n > 0 && impl && g_step_launch) {
+        if (impl->wave_step(c, d, adam_epilogue(params_flat, adam), &rc)) return rc ? rc : zero_empty_sets(sets, n_sets, c.net.nout, st);
+    }
+    // ---- every other case: the collocation call, then d as a call of its own into the same gradient, then the update -- the same bits
+    rc = pinn_wave2d_loss_grad(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, E, mu, rho, plane_strain, term_weights, loss_terms_out,
+                               grad_flat_out, accumulate, precision_mode, workspace, ws_bytes, stream);
+    if (rc) return rc;
+    if ((rc = zero_empty_sets(sets, n_sets, c.net.nout, st))) return rc;
+    d.accumulate = 1;
+    if (n > 0) d.weights_packed = 1;      // (an empty collocation batch packed nothing)
+    d.x = trac_x;                         // (a multi-set call's own points are those of a non-empty set; the largest size sizes its plan)
+    d.y = trac_y;
+    d.t = trac_t;
+    d.n = (long)trac_n;
+    for (int k = 0; k < n_sets; ++k)
+        if (sets[k].n > d.n) d.n = (long)sets[k].n;
+    if (impl) {
+        rc = impl->run[CALL_DATA_LOSS_GRAD](d);
+    } else {      // PINN_PREC_FP32: one set after the other into the same gradient
+        for (int k = 0; k < d.nsets && !rc; ++k)
+            if (d.sets[k].n > 0) rc = fp32_call(set_call(d, d.sets[k], false), CALLS[d.sets[k].head == 2 ? CALL_WAVE_TRACTION_LOSS_GRAD : CALL_DATA_LOSS_GRAD]);
+    }
+    if (rc) return rc;
     return adam_tail(params_flat, layers, n_layers, grad_flat_out, adam, stream);
 }
 
@@ -891,7 +989,7 @@ int pinn_plate2d_step(float* params_flat, const int* layers, int n_layers, const
     if (rc) return rc;
     if (hole_n > 0 && (!hole_x || !hole_y || !hole_t || !hole_frozen_and_normals || !hole_weights || !hole_loss_terms_out)) return PINN_ERR_NULL;
     // ---- the one-launch form (fused_step_kernel<..., NSC = 5>): the five-stream collocation set and the hole-traction set
-    if (n > 0 && hole_n > 0 && frozen_streams && term_weights && loss_terms_out && grad_flat_out) {
+    if (n > 0 && hole_n > 0 && frozen_streams && term_weights && loss_terms_out && grad_flat_out && g_step_launch) {
         Call c;
         const Impl* impl = nullptr;
         rc = prepare(params_flat, layers, n_layers, x, y, t, n, lb, ub, normalize, precision_mode, workspace, ws_bytes, stream, c, impl);

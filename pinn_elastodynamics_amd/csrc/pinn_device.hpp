@@ -232,6 +232,8 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 // HEAD_FIELDS : forward only, writes all NS streams of the outputs
 // HEAD_PLATE  : 5 streams (value, x, y, t, tt), composite P + D*N with frozen D/P streams in `aux`, plane-stress residuals (PLATE:358-439)
 // HEAD_TRACTION: 1 stream, hole traction of the composite (PLATE:452-461); aux = D0[5], P0[5], nx, ny per point
+// HEAD_TRACTION_WAVE: 1 stream, 7 outputs: traction vector of the wave net's own stresses on a boundary with per-point normals, less a
+//               per-point target (net_surf_var, INF:267-276); aux = nx, ny, tx, ty per point ([4][n]), normals used as given
 // HEAD_STREAMS: 5 streams, sum_{s,o} w[s][o] (Y[s][o] - target[s][o])^2 -- the D / P pre-training losses (PLATE:194-215)
 // HEAD_NC3D   : 5 first-order streams (value, x, y, z, t), 4 inputs, 12 outputs: 3-D Navier-Cauchy residuals (build-side extension of
 //               INF:221-265, stated in oracle/nc3d_oracle.py; BASELINE.json configs[4])
@@ -261,7 +263,7 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 //               MATERIAL_SUMS_3D fp64 sums -- twelve squares, twelve moments (pinn_nc3d_material_sums)
 enum { HEAD_WAVE = 0, HEAD_DATA = 1, HEAD_FIELDS = 2, HEAD_PLATE = 3, HEAD_TRACTION = 4, HEAD_STREAMS = 5, HEAD_NC3D = 6, HEAD_DATA3D = 7,
        HEAD_FIELDS3D = 8, HEAD_SCORE = 9, HEAD_SCORE_PLATE = 10, HEAD_SCORE3D = 11, HEAD_PREDICT = 12, HEAD_PREDICT_PLATE = 13, HEAD_MATERIAL = 14,
-       HEAD_MATERIAL_PLATE = 15, HEAD_MATERIAL3D = 16 };
+       HEAD_MATERIAL_PLATE = 15, HEAD_MATERIAL3D = 16, HEAD_TRACTION_WAVE = 17 };
 constexpr int MATERIAL_SUMS = 14;           // HEAD_MATERIAL: sums per record (PINN_MATERIAL_SUMS)
 constexpr int MATERIAL_SUMS_PLATE = 12;     // HEAD_MATERIAL_PLATE (PINN_MATERIAL_SUMS_PLATE)
 constexpr int MATERIAL_SUMS_3D = 24;        // HEAD_MATERIAL3D (PINN_MATERIAL_SUMS_NC3D)
@@ -302,7 +304,7 @@ struct ChainArgs {
     long Z_tile_stride;
     float* loss_part;          // [total waves][8 or LOSS_SLOTS_3D] per-wave partial sums of squares
     float* fields_out;         // HEAD_FIELDS: [NS*nout][n]  (Y, dY/dx, dY/dy, dY/dt [, d2Y/dt2]);  score heads: [n];  predict heads: [8][n]
-    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_PREDICT_PLATE / HEAD_MATERIAL_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or null
+    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_PREDICT_PLATE / HEAD_MATERIAL_PLATE: [2 nets (D,P)][5 streams][5 fields][n]; HEAD_TRACTION: [12][n]; HEAD_TRACTION_WAVE: [4][n]; HEAD_STREAMS: targets [5][nout][n] or null
     float w5[5][8];            // HEAD_STREAMS: per (stream, output) weights, max-normalised
     double* moment_part;       // material heads: [total waves][material_sums_of(HEAD)] per-wave sums
 };
@@ -1031,6 +1033,22 @@ struct Chain {
                     adj[0][nb][2] = gx * nx * D0[2];
                     adj[0][nb][3] = gy * ny * D0[3];
                     adj[0][nb][4] = (gx * ny + gy * nx) * D0[4];
+                } else if constexpr (HEAD == HEAD_TRACTION_WAVE) {
+                    // net_surf_var INF:267-276 on the net's own stresses (outputs u, v, ut, vt, s11, s22, s12), less the prescribed traction;
+                    // aux rows: nx[0], ny[1], tx[2], ty[3].  The normals are used as given (not normalised).
+                    const float nx = a.aux[0L * a.n + pidx[nb]], ny = a.aux[1L * a.n + pidx[nb]];
+                    const float rx = Y[0][nb][4] * nx + Y[0][nb][6] * ny - a.aux[2L * a.n + pidx[nb]];
+                    const float ry = Y[0][nb][6] * nx + Y[0][nb][5] * ny - a.aux[3L * a.n + pidx[nb]];
+                    if (q == 0) {
+                        lsum[0] += vm * rx * rx;
+                        lsum[1] += vm * ry * ry;
+                    }
+                    const float gx = 2.0f * a.tw[0] * rx * vm, gy = 2.0f * a.tw[1] * ry * vm;
+#pragma unroll
+                    for (int o = 0; o < 8; ++o) adj[0][nb][o] = 0.0f;
+                    adj[0][nb][4] = gx * nx;
+                    adj[0][nb][5] = gy * ny;
+                    adj[0][nb][6] = gx * ny + gy * nx;
                 } else if constexpr (HEAD == HEAD_STREAMS) {
                     // sum_{s,o} w[s][o] (Y[s][o] - target[s][o])^2 ; lsum[o] accumulates the weight-normalised sum over streams
 #pragma unroll
@@ -1525,7 +1543,7 @@ __global__ __launch_bounds__(256) void reduce_grad_kernel(const float* partial, 
 // Fused-path epilogue: reduce_grad_kernel's blocks plus one extra block per point set (the last nsets blocks) that do
 // reduce_loss_kernel's job, so that a call ends with one launch instead of two (the small configurations are bound by the chain
 // of short launches).  loss_part is [wave][slots][8] (set k in slot k); set k's sums go to loss_out.p[k][0..nterms).
-struct LossOuts { float* p[4]; };
+struct LossOuts { float* p[4]; int nt[4]; };      // nt[k] > 0: set k has that many terms instead of the call's `nterms` (a traction set: 2)
 template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void reduce_grad_loss_kernel(const float* partial, int nchunks, int nparams, float scale, float* grad,
                                                                int accumulate, const float* loss_part, long nwaves, int nterms, int nsets,
@@ -1542,6 +1560,7 @@ __global__ __launch_bounds__(256) void reduce_grad_loss_kernel(const float* part
     const int grad_blocks = (int)gridDim.x - nsets;
     if ((int)blockIdx.x >= grad_blocks) {
         const int k = (int)blockIdx.x - grad_blocks;
+        if (loss_out.nt[k] > 0) nterms = loss_out.nt[k];
         const int term = threadIdx.x >> 5, sub = threadIdx.x & 31;
         double s = 0.0;
         if (term < nterms)
@@ -1663,7 +1682,7 @@ __global__ __launch_bounds__(256) void reduce_step_kernel(StepPart A, StepPart B
         const int k = (int)blockIdx.x - grad_blocks - 1;          // -1: the collocation set, 0..nsets-1: the side sets
         const float* lp = k < 0 ? A.loss_part : B.loss_part;
         const long nw = k < 0 ? A.nwaves : B.nwaves;
-        const int slots = k < 0 ? 1 : slots_b, slot = k < 0 ? 0 : k, nterms = k < 0 ? nterms_a : nterms_b;
+        const int slots = k < 0 ? 1 : slots_b, slot = k < 0 ? 0 : k, nterms = k < 0 ? nterms_a : (loss_b.nt[k] > 0 ? loss_b.nt[k] : nterms_b);
         float* out = k < 0 ? loss_a : loss_b.p[k];
         const int term = threadIdx.x >> 5, sub = threadIdx.x & 31;
         double s = 0.0;

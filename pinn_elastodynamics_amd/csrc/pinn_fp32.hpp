@@ -35,7 +35,7 @@ struct Fp32Args {
     float w5[5][8];            // HEAD_STREAMS: weight per (stream, output)
     float w5n[5][8];           // ... divided by the largest: the loss sums of that head are reported weight-normalised
     const float* targets;      // data heads: [nout][n] or nullptr
-    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_MATERIAL_PLATE: frozen streams [2][5][5][n]; HEAD_TRACTION: [12][n]; HEAD_STREAMS: targets [5][nout][n] or nullptr
+    const float* aux;          // HEAD_PLATE / HEAD_SCORE_PLATE / HEAD_MATERIAL_PLATE: frozen streams [2][5][5][n]; HEAD_TRACTION: [12][n]; HEAD_TRACTION_WAVE: [4][n]; HEAD_STREAMS: targets [5][nout][n] or nullptr
     float* S;                  // [nl+1][ns][hr][m]: S_0 = inputs and tangent seeds (first din rows), S_l = state behind hidden layer l
     float* Z;                  // [nl+1][ns][hr][m]: Z_l = adjoint of the pre-activations of weight layer l (Z_nl: nout rows)
     float* fsq;                // [FP32_TERMS][m]: squared residuals of the pass
@@ -468,6 +468,18 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             adj[0][2] = gx * nx * D0[2];
             adj[0][3] = gy * ny * D0[3];
             adj[0][4] = (gx * ny + gy * nx) * D0[4];
+        } else if (a.head == HEAD_TRACTION_WAVE) {
+            // net_surf_var INF:267-276 on the net's own stresses (outputs 4, 5, 6 = s11, s22, s12), less the prescribed traction;
+            // aux rows: nx[0], ny[1], tx[2], ty[3], normals used as given
+            const float nx = a.aux[0L * a.n + gp], ny = a.aux[1L * a.n + gp];
+            const float rx = Y[0][4] * nx + Y[0][6] * ny - a.aux[2L * a.n + gp];
+            const float ry = Y[0][6] * nx + Y[0][5] * ny - a.aux[3L * a.n + gp];
+            a.fsq[0L * a.m + p] = rx * rx;
+            a.fsq[1L * a.m + p] = ry * ry;
+            const float gx = 2.0f * a.tw[0] * rx, gy = 2.0f * a.tw[1] * ry;
+            adj[0][4] = gx * nx;
+            adj[0][5] = gy * ny;
+            adj[0][6] = gx * ny + gy * nx;
         } else if (a.head == HEAD_STREAMS) {
             // sum_{s,o} w[s][o] (Y[s][o] - target[s][o])^2 : the loss term of output o collects its streams (PLATE:194-215)
             for (int o = 0; o < NO; ++o) {

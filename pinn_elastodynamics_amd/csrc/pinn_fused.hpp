@@ -79,8 +79,9 @@ struct FusedArgs {
     const float* set_targets[4];
     long set_n[4];
     float set_tw[4][16];       // (3-input nets: 8 used; the 3-D data head: up to 16 outputs)
-    int set_head[4];           // 0: data head (targets, output weights); 1: hole traction of the plate's composite fields (PLATE:452-461)
-    const float* set_aux[4];   // traction sets: [12][n] = D0[5], P0[5], nx, ny of the set's points
+    int set_head[4];           // set kind -- 0: data head (targets, output weights); 1: hole traction of the plate's composite fields (PLATE:452-461);
+                               // 2: traction of the wave net's own stresses with per-point normals and targets (INF:267-276), weights set_tw[k][0..1]
+    const float* set_aux[4];   // kind 1: [12][n] = D0[5], P0[5], nx, ny of the set's points; kind 2: [4][n] = nx, ny, tx, ty (row stride set_n[k])
     u32x4* scratch;            // [gridDim.x * TILES][SCRATCH_BYTES]: per-tile images of the parked states
     float* loss_part;          // [gridDim.x * TILES][8]
     float* partial;            // [gridDim.x][nparams]
@@ -2915,6 +2916,22 @@ struct Fused {
             adj[0][2] = gx * nx * D0[2];
             adj[0][3] = gy * ny * D0[3];
             adj[0][4] = (gx * ny + gy * nx) * D0[4];
+        } else if (a.set_head[set] == 2) {
+            // net_surf_var INF:267-276 on the wave net's own stresses (outputs u, v, ut, vt, s11, s22, s12), less the prescribed traction
+            // (chain_kernel's HEAD_TRACTION_WAVE); the set's aux rows: nx[0], ny[1], tx[2], ty[3], normals used as given
+            const float* aux = a.set_aux[set];
+            const long nn = a.set_n[set];
+            const float nx = aux[pidx], ny = aux[nn + pidx];
+            const float rx = Y[0][4] * nx + Y[0][6] * ny - aux[2L * nn + pidx];
+            const float ry = Y[0][6] * nx + Y[0][5] * ny - aux[3L * nn + pidx];
+            if (q == 0) {
+                lsum[0] += vm * rx * rx;
+                lsum[1] += vm * ry * ry;
+            }
+            const float gx = 2.0f * in_loop(a.set_tw[set][0]) * rx * vm, gy = 2.0f * in_loop(a.set_tw[set][1]) * ry * vm;
+            adj[0][4] = gx * nx;
+            adj[0][5] = gy * ny;
+            adj[0][6] = gx * ny + gy * nx;
         } else {
 #pragma unroll
             for (int o = 0; o < NOG; ++o) {

@@ -21,7 +21,8 @@ struct DataSet {                // one value-only point set of pinn_data_loss_gr
     float tw[16];              // (3-input nets: 8 used; the 3-D data head: up to 16 outputs)
     const float* z = nullptr;  // 4-input nets (the 3-D side sets)
     float* loss_out;
-    int head = 0;              // 0: sum_o w_o (Y_o - target_o)^2;  1: hole traction of the plate's composite fields (HEAD_TRACTION), `aux` = [12][n]
+    int head = 0;              // 0: sum_o w_o (Y_o - target_o)^2;  1: hole traction of the plate's composite fields (HEAD_TRACTION), `aux` = [12][n];
+                               // 2: traction of the wave net's own stresses (HEAD_TRACTION_WAVE), `aux` = [4][n] = nx, ny, tx, ty, weights tw[0..1]
     const float* aux = nullptr;
 };
 
@@ -100,7 +101,7 @@ struct Call {
     int adj_shift = 0;         // PINN_ADJOINT_SHIFT(k): adjoint seeds scaled by 2^-k inside the kernels, the gradient by 2^k at the reduction
     int weights_packed = 0;    // skip the repack: the workspace already holds the packed form of `params` (same net / precision mode)
     int use_fused = 1;         // 1: prefer the fused kernel where it applies (default), 0: force the two-kernel path
-    int one_stream_head = 0;   // single-set one-stream calls: 0 = data head, 1 = hole traction (fused one-stream kernel, see DataSet::head)
+    int one_stream_head = 0;   // single-set one-stream calls, the set's kind: 0 = data head, 1 = hole traction, 2 = wave traction (fused one-stream kernel, see DataSet::head)
     int fast_state = 0;        // PINN_FLAG_STATE_FP16: fused kernel parks its states as fp16 high parts only (faster, less accurate at trained weights)
 };
 
@@ -115,11 +116,11 @@ extern int g_fused_grid_cap;
 // ---- The single-set per-point calls of the library, said ONCE: one id per call and one row of CALLS with everything the host knows about it.
 // Host::run<ID> builds the call's launch sequence from its row, Impl carries one run per id, and the entry points of pinn_capi.hip take
 // the streams, inputs, terms and output count of their checks and of the PINN_PREC_FP32 path from the same row.  The key is the call, not the
-// head: HEAD_FIELDS serves the fields (4 streams) and the streams (5), HEAD_DATA and HEAD_TRACTION both take the one-stream fused kind.
+// head: HEAD_FIELDS serves the fields (4 streams) and the streams (5), HEAD_DATA, HEAD_TRACTION and HEAD_TRACTION_WAVE all take the one-stream fused kind.
 enum CallId {
     CALL_WAVE_LOSS_GRAD, CALL_DATA_LOSS_GRAD, CALL_WAVE_FIELDS, CALL_WAVE_SCORE, CALL_WAVE_PREDICT, CALL_WAVE_MATERIAL,
     CALL_NET_STREAMS, CALL_PLATE_LOSS_GRAD, CALL_PLATE_SCORE, CALL_PLATE_PREDICT, CALL_PLATE_MATERIAL, CALL_TRACTION_LOSS_GRAD, CALL_STREAM_LOSS_GRAD,
-    CALL_NC3D_LOSS_GRAD, CALL_NC3D_SCORE, CALL_NC3D_DATA_LOSS_GRAD, CALL_NC3D_FIELDS, CALL_NC3D_MATERIAL, N_CALLS
+    CALL_NC3D_LOSS_GRAD, CALL_NC3D_SCORE, CALL_NC3D_DATA_LOSS_GRAD, CALL_NC3D_FIELDS, CALL_NC3D_MATERIAL, CALL_WAVE_TRACTION_LOSS_GRAD, N_CALLS
 };
 // LOSS_GRAD: the fused kernel of the row's kind where it applies, else chain + weight-gradient kernels (loss sums and gradient);
 // FORWARD: one chain launch of a forward-only head that writes per point; FORWARD_SUMS: the same + the one-workgroup fp64 final sum of the
@@ -142,29 +143,30 @@ struct CallRow {
     bool needs_aux;            // the head reads c.aux at every point (frozen streams, hole normals): a required argument of a call with points
     int nb;                    // blocks per wave of the chain launch (0: Host::nb<ns>())
     bool fused;                // a loss + gradient call that takes the fused kernel of kind <ns, din> where one is compiled for the net (with_fused)
-    bool one_stream_head;      // the one-stream fused kernel runs it as a hole-traction set (Call::one_stream_head)
+    int one_stream_head;       // the set kind the one-stream fused kernel runs it as: 0 data, 1 hole traction, 2 wave traction (Call::one_stream_head)
     bool counted;              // a PINN_PREC_FP32 run of it counts in g_path_counts (a loss + gradient call; historically also fields and streams)
 };
 constexpr CallRow CALLS[N_CALLS] = {
     //                        head                 ns din nout terms shape               split  tw     aux    nb          fused  1-str  counted
-    {CALL_WAVE_LOSS_GRAD,     HEAD_WAVE,           4, 3,  7,   7,    SHAPE_LOSS_GRAD,    false, true,  false, 0,          true,  false, true},
-    {CALL_DATA_LOSS_GRAD,     HEAD_DATA,           1, 3,  0,   0,    SHAPE_LOSS_GRAD,    false, true,  false, 0,          true,  false, true},
-    {CALL_WAVE_FIELDS,        HEAD_FIELDS,         4, 3,  0,   0,    SHAPE_FORWARD,      false, false, false, 0,          false, false, true},
-    {CALL_WAVE_SCORE,         HEAD_SCORE,          4, 3,  7,   7,    SHAPE_FORWARD,      false, true,  false, 0,          false, false, false},
-    {CALL_WAVE_PREDICT,       HEAD_PREDICT,        3, 3,  7,   0,    SHAPE_FORWARD,      false, false, false, NB_PREDICT, false, false, false},
-    {CALL_WAVE_MATERIAL,      HEAD_MATERIAL,       4, 3,  7,   0,    SHAPE_FORWARD_SUMS, false, false, false, 0,          false, false, false},
-    {CALL_NET_STREAMS,        HEAD_FIELDS,         5, 3,  0,   0,    SHAPE_FORWARD,      true,  false, false, 0,          false, false, true},
-    {CALL_PLATE_LOSS_GRAD,    HEAD_PLATE,          5, 3,  5,   5,    SHAPE_LOSS_GRAD,    true,  true,  true,  0,          true,  false, true},
-    {CALL_PLATE_SCORE,        HEAD_SCORE_PLATE,    5, 3,  5,   5,    SHAPE_FORWARD,      true,  true,  true,  0,          false, false, false},
-    {CALL_PLATE_PREDICT,      HEAD_PREDICT_PLATE,  3, 3,  5,   0,    SHAPE_FORWARD,      true,  false, true,  NB_PREDICT, false, false, false},
-    {CALL_PLATE_MATERIAL,     HEAD_MATERIAL_PLATE, 5, 3,  5,   0,    SHAPE_FORWARD_SUMS, true,  false, true,  0,          false, false, false},
-    {CALL_TRACTION_LOSS_GRAD, HEAD_TRACTION,       1, 3,  5,   2,    SHAPE_LOSS_GRAD,    true,  true,  true,  0,          true,  true,  true},
-    {CALL_STREAM_LOSS_GRAD,   HEAD_STREAMS,        5, 3,  0,   0,    SHAPE_LOSS_GRAD,    true,  true,  false, 0,          false, false, true},
-    {CALL_NC3D_LOSS_GRAD,     HEAD_NC3D,           5, 4,  12,  12,   SHAPE_LOSS_GRAD,    true,  true,  false, 0,          true,  false, true},
-    {CALL_NC3D_SCORE,         HEAD_SCORE3D,        5, 4,  12,  12,   SHAPE_FORWARD,      true,  true,  false, 0,          false, false, false},
-    {CALL_NC3D_DATA_LOSS_GRAD, HEAD_DATA3D,        1, 4,  0,   0,    SHAPE_LOSS_GRAD,    true,  true,  false, 0,          true,  false, true},
-    {CALL_NC3D_FIELDS,        HEAD_FIELDS3D,       5, 4,  0,   0,    SHAPE_FORWARD,      true,  false, false, 0,          false, false, true},
-    {CALL_NC3D_MATERIAL,      HEAD_MATERIAL3D,     5, 4,  12,  0,    SHAPE_FORWARD_SUMS, true,  false, false, 0,          false, false, false},
+    {CALL_WAVE_LOSS_GRAD,     HEAD_WAVE,           4, 3,  7,   7,    SHAPE_LOSS_GRAD,    false, true,  false, 0,          true,  0,     true},
+    {CALL_DATA_LOSS_GRAD,     HEAD_DATA,           1, 3,  0,   0,    SHAPE_LOSS_GRAD,    false, true,  false, 0,          true,  0,     true},
+    {CALL_WAVE_FIELDS,        HEAD_FIELDS,         4, 3,  0,   0,    SHAPE_FORWARD,      false, false, false, 0,          false, 0,     true},
+    {CALL_WAVE_SCORE,         HEAD_SCORE,          4, 3,  7,   7,    SHAPE_FORWARD,      false, true,  false, 0,          false, 0,     false},
+    {CALL_WAVE_PREDICT,       HEAD_PREDICT,        3, 3,  7,   0,    SHAPE_FORWARD,      false, false, false, NB_PREDICT, false, 0,     false},
+    {CALL_WAVE_MATERIAL,      HEAD_MATERIAL,       4, 3,  7,   0,    SHAPE_FORWARD_SUMS, false, false, false, 0,          false, 0,     false},
+    {CALL_NET_STREAMS,        HEAD_FIELDS,         5, 3,  0,   0,    SHAPE_FORWARD,      true,  false, false, 0,          false, 0,     true},
+    {CALL_PLATE_LOSS_GRAD,    HEAD_PLATE,          5, 3,  5,   5,    SHAPE_LOSS_GRAD,    true,  true,  true,  0,          true,  0,     true},
+    {CALL_PLATE_SCORE,        HEAD_SCORE_PLATE,    5, 3,  5,   5,    SHAPE_FORWARD,      true,  true,  true,  0,          false, 0,     false},
+    {CALL_PLATE_PREDICT,      HEAD_PREDICT_PLATE,  3, 3,  5,   0,    SHAPE_FORWARD,      true,  false, true,  NB_PREDICT, false, 0,     false},
+    {CALL_PLATE_MATERIAL,     HEAD_MATERIAL_PLATE, 5, 3,  5,   0,    SHAPE_FORWARD_SUMS, true,  false, true,  0,          false, 0,     false},
+    {CALL_TRACTION_LOSS_GRAD, HEAD_TRACTION,       1, 3,  5,   2,    SHAPE_LOSS_GRAD,    true,  true,  true,  0,          true,  1,     true},
+    {CALL_STREAM_LOSS_GRAD,   HEAD_STREAMS,        5, 3,  0,   0,    SHAPE_LOSS_GRAD,    true,  true,  false, 0,          false, 0,     true},
+    {CALL_NC3D_LOSS_GRAD,     HEAD_NC3D,           5, 4,  12,  12,   SHAPE_LOSS_GRAD,    true,  true,  false, 0,          true,  0,     true},
+    {CALL_NC3D_SCORE,         HEAD_SCORE3D,        5, 4,  12,  12,   SHAPE_FORWARD,      true,  true,  false, 0,          false, 0,     false},
+    {CALL_NC3D_DATA_LOSS_GRAD, HEAD_DATA3D,        1, 4,  0,   0,    SHAPE_LOSS_GRAD,    true,  true,  false, 0,          true,  0,     true},
+    {CALL_NC3D_FIELDS,        HEAD_FIELDS3D,       5, 4,  0,   0,    SHAPE_FORWARD,      true,  false, false, 0,          false, 0,     true},
+    {CALL_NC3D_MATERIAL,      HEAD_MATERIAL3D,     5, 4,  12,  0,    SHAPE_FORWARD_SUMS, true,  false, false, 0,          false, 0,     false},
+    {CALL_WAVE_TRACTION_LOSS_GRAD, HEAD_TRACTION_WAVE, 1, 3, 7, 2,   SHAPE_LOSS_GRAD,    false, true,  true,  0,          true,  2,     true},
 };
 constexpr bool calls_consistent() {
     for (int i = 0; i < N_CALLS; ++i) {
@@ -175,6 +177,7 @@ constexpr bool calls_consistent() {
         if ((r.din == 4) != head_is_3d(r.head)) return false;
         if (r.with_tw != (r.shape == SHAPE_LOSS_GRAD || head_is_score(r.head))) return false;
         if ((r.fused || r.one_stream_head) && r.shape != SHAPE_LOSS_GRAD) return false;
+        if (r.one_stream_head < 0 || r.one_stream_head > 2 || (r.one_stream_head && (r.ns != 1 || !r.fused || !r.needs_aux))) return false;      // a set kind of the one-stream kernel
     }
     return true;
 }
@@ -211,6 +214,8 @@ inline Call set_call(const Call& c, const DataSet& s, bool first) {
     r.targets = s.targets;
     for (int i = 0; i < 8; ++i) r.tw[i] = s.tw[i];
     r.loss_out = s.loss_out;
+    r.aux = s.aux;                     // (a traction set of the wave family: DataSet::head == 2)
+    r.one_stream_head = s.head;
     r.accumulate = c.accumulate || !first;
     r.weights_packed = c.weights_packed || !first;
     return r;
@@ -655,7 +660,7 @@ struct Host {
         a.aux = c.aux;
         a.dbg = c.dbg_stamps;
         float twmax = 0.0f;
-        LossOuts lo = {{nullptr, nullptr, nullptr, nullptr}};
+        LossOuts lo = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
         int nsets = 1;
         if constexpr (NS == 1) {
             DataSet sets[4];
@@ -678,6 +683,7 @@ struct Host {
                 for (int i = 0; i < NTW; ++i) a.set_tw[k][i] = twmax > 0.0f ? sets[k].tw[i] / twmax : 0.0f;
                 s0 += (sets[k].n + 16 * F::TILES - 1) / (16 * F::TILES);
                 lo.p[k] = sets[k].loss_out;
+                lo.nt[k] = sets[k].head == 2 ? 2 : 0;      // (a wave traction set reports its two sums, whatever the call's term count)
             }
             for (int k = nsets; k <= 4; ++k) a.set_step0[k] = s0;
             a.nsets = nsets;
@@ -852,7 +858,9 @@ struct Host {
         bool first = true;
         for (int k = 0; k < c.nsets; ++k) {
             if (c.sets[k].n <= 0) continue;
-            if (const int rc = loss_grad<1, HEAD_DATA>(set_call(c, c.sets[k], first), c.net.nout)) return rc;
+            const Call s = set_call(c, c.sets[k], first);
+            // (a traction set of the step, DataSet::head == 2: its own head and two terms)
+            if (const int rc = c.sets[k].head == 2 ? loss_grad<1, HEAD_TRACTION_WAVE>(s, 2) : loss_grad<1, HEAD_DATA>(s, c.net.nout)) return rc;
             first = false;
         }
         return 0;
@@ -891,9 +899,9 @@ struct Host {
             const int nterms = R.nterms ? R.nterms : c.net.nout;
             if constexpr (R.fused) {
                 int rc = 0;
-                if constexpr (R.one_stream_head) {
-                    Call t = c;      // the hole-traction set: the one-stream kernel's head takes the set's kind from the set table
-                    t.one_stream_head = 1;
+                if constexpr (R.one_stream_head != 0) {
+                    Call t = c;      // a traction set: the one-stream kernel's head takes the set's kind from the set table
+                    t.one_stream_head = R.one_stream_head;
                     if (c.use_fused && try_fused<R.ns, R.din>(t, &rc, nterms)) return rc;
                 } else if (c.use_fused && try_fused<R.ns, R.din>(c, &rc, nterms)) {
                     return rc;

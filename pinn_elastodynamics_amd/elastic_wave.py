@@ -25,7 +25,7 @@ from . import material
 from .model_base import ShardedSetsModel
 from .net_api import write_checkpoint
 # (the optimizer and parameter helpers lived in this module before optim.py: tools and tests import them from here)
-from .optim import (BFGS_BACKENDS, LbfgsResult, all_reduce_sum, check_backend, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device,  # noqa: F401
+from .optim import (BFGS_BACKENDS, LbfgsResult, all_reduce_sum, check_backend, device_array, evaluate_with_finite_gradient, lbfgs_hip, lbfgs_on_device,  # noqa: F401
                     pack_params, relax_adjoint_shift, unpack_params, xavier_init)
 from .refine import Candidates, candidate_array, pair_replacements, refine_sharded_set, schedule, score_weights  # noqa: F401
 from .validate import PredictMixin, schedule as validate_schedule
@@ -53,11 +53,17 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
 
     def __init__(self, Collo, SRC, IC, UP, uv_layers, lb, ub, ExistModel=0, modelDir='', *, case="infinite",
                  FIX=None, precision="f16x3", engine=None, seed=1111, process_group=None, verbose=True,
-                 E=2.5, mu=0.25, rho=1.0, always_reduce=False, shard_as=None, collective="rccl", step_call=True, p2p_timeout_s=None):
+                 E=2.5, mu=0.25, rho=1.0, always_reduce=False, shard_as=None, collective="rccl", step_call=True, p2p_timeout_s=None,
+                 TRAC=None, trac_weight=None):
+        """``TRAC``: a traction boundary set [n, 5] = (x, y, t, nx, ny) -- traction-free: a cavity, an inclined or curved free surface -- or
+        [n, 7] = (x, y, t, nx, ny, tx, ty) with a prescribed traction per point (pointsets.circle_traction_set / traction_set).  Its term
+        loss_TRAC = <r_x^2> + <r_y^2>, r = sigma n - t of net_surf_var (INF:267-276), enters the total with ``trac_weight`` (default: what the
+        case's layout puts on SRC).  The normals are used as given.  Without it the model is exactly the one without the keyword."""
         self.count = 0                      # callback counter (INF:26)
         self._step_call = bool(step_call)   # False: the step as separate library calls (collocation, side sets, Adam) -- the same bits; for A / B timing
         self._shift_state = {}              # adjoint-shift bookkeeping of evaluate_with_finite_gradient
         self.loss_rec = []                  # SEMI:39
+        self.trac_rec = []                  # loss_TRAC per step of train() (models with a traction set)
         self.case = case
         self.layout = LOSS_LAYOUT[case]
         self.normalize = case == "infinite"            # INF:191 vs SEMI:198 / CONF:235
@@ -79,9 +85,29 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
         self._add_side("NB", UP, (5, 6))                           # s22,s12 = 0 on the free edge  INF:117-118
         self._add_side("FIX", FIX, (0, 1))                         # u,v = 0 on the fixed edges    CONF:145-146
         self.SRC, self.IC, self.UP, self.FIX = SRC, IC, UP, FIX
+        self._add_traction(TRAC, trac_weight)                      # sigma n = t on a boundary with normals INF:267-276
 
-        self._buf = torch.zeros(self.n_params + 8 * len(_SLOTS), dtype=torch.float32, device=self.device)
+        self._buf = torch.zeros(self.n_params + 8 * len(self.SLOTS), dtype=torch.float32, device=self.device)
         self._init_collective(collective, p2p_timeout_s)
+
+    def _add_traction(self, TRAC, trac_weight):
+        """Register the traction set: one more slot ("TRAC", sums r_x^2, r_y^2 in its columns 0, 1) behind the five every model has -- per
+        instance, a model without the set keeps five --, this rank's rows and their [4, m] = nx, ny, tx, ty on the device, sharded as _add_side
+        shards (the kernels weight with the global 1/n)."""
+        self.TRAC = TRAC
+        if TRAC is None or np.asarray(TRAC).shape[0] == 0:
+            return
+        A = np.asarray(TRAC, dtype=np.float64)
+        if A.ndim != 2 or A.shape[1] not in (5, 7):
+            raise ValueError("TRAC is [n, 5] = (x, y, t, nx, ny) or [n, 7] = (x, y, t, nx, ny, tx, ty)")
+        self.SLOTS = _SLOTS + ("TRAC",)
+        self.layout = dict(self.layout, TRAC=float(self.layout["SRC"] if trac_weight is None else trac_weight))
+        n_glob = A.shape[0]
+        s, e = self._shard(0, n_glob)
+        A = A[s:e]
+        aux = np.zeros((4, A.shape[0]), dtype=np.float32)
+        aux[:A.shape[1] - 3] = A[:, 3:].T
+        self._sides["TRAC"] = tuple(self._device_columns(A[:, k] for k in range(3))) + (device_array(aux, self.device), (0, 1), n_glob)
 
     def set_weights(self, weights, biases):
         self.theta.copy_(torch.from_numpy(pack_params(weights, biases)).to(self.device))
@@ -229,7 +255,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
     def _loss_and_grad(self, idx_start, idx_end, sums_out=None, adam=None):
         """Fills self._buf = [grad (P) | 8 floats per slot] with this rank's partial sums, then
         all-reduces.  Everything stays on the device.  Single process only: ``sums_out`` (a view of
-        8*len(_SLOTS) floats, zero where no set exists) receives the sums directly instead of the tail of the buffer.
+        8*len(self.SLOTS) floats, zero where no set exists) receives the sums directly instead of the tail of the buffer.
         ``adam = (learning_rate, step)``: the caller wants the Adam update behind this gradient; where the whole evaluation is ONE library call
         (engine.wave_step: collocation set + side sets in one launch, one reduction) and no collective stands in between, the update rides in
         that reduction -- returns True then (the caller skips its own adam_step), False otherwise."""
@@ -238,7 +264,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
         s, e = self._shard(idx_start, idx_end)
         # slots this call's kernels (over)write: the collocation slot if this rank has rows of the block, every active non-empty side set
         writes = {0} if e > s else set()
-        for k, name in enumerate(_SLOTS[1:], start=1):
+        for k, name in enumerate(self.SLOTS[1:], start=1):
             if name in self._sides and lay[name] != 0.0 and self._sides[name][0].numel() > 0:
                 writes.add(k)
         if sums_out is None or self._reduce:
@@ -246,7 +272,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
             # slots of skipped sets must read zero (getloss toggles the NB weight; a rank without rows of a set contributes nothing to the
             # reduced sum).  The kernels overwrite their slots, so only a slot that was written before and is NOT written now needs zeroing
             # -- in a training loop the same slots are written every step and no launch is spent here.
-            stale = getattr(self, "_slots_dirty", set(range(len(_SLOTS)))) - writes
+            stale = getattr(self, "_slots_dirty", set(range(len(self.SLOTS)))) - writes
             for k in stale:
                 sums[8 * k:8 * k + 8].zero_()
             self._slots_dirty = set(writes)
@@ -255,7 +281,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
                 # (a set or block with fewer rows than ranks: _shard gives e == s here).  Such a slot must be zeroed again before the next
                 # collective, or the old total is added into it.  Which slots are written somewhere is a global fact (a side set is
                 # registered on every rank with its global row count): mark them all.
-                self._slots_dirty |= ({0} if n_blk > 0 else set()) | {k for k, name in enumerate(_SLOTS[1:], start=1)
+                self._slots_dirty |= ({0} if n_blk > 0 else set()) | {k for k, name in enumerate(self.SLOTS[1:], start=1)
                                                                        if name in self._sides and lay[name] != 0.0}
         else:
             sums = sums_out
@@ -272,13 +298,21 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
             for o in cols:
                 ow[o] = lay[name] / n
             side.append((x, y, t, tg, ow, sums[8 * k:8 * k + 8]))
+        # the traction set (slot "TRAC"): this rank's rows, if it has any -- a rank whose shard of the set is empty makes no call for it
+        trac = None
+        if "TRAC" in self._sides and lay["TRAC"] != 0.0 and self._sides["TRAC"][0].numel() > 0:
+            x, y, t, aux, _, n = self._sides["TRAC"]
+            k = self.SLOTS.index("TRAC")
+            trac = (x, y, t, aux, [lay["TRAC"] / n] * 2, sums[8 * k:8 * k + 8])
         stepped = False
-        if e > s and 1 <= len(side) <= 4 and hasattr(eng, "wave_step") and self._step_call:
-            # the whole evaluation as ONE library call: repack | one persistent launch for all sets | one reduction (+ Adam)
+        if e > s and 1 <= len(side) + (trac is not None) <= 4 and hasattr(eng, "wave_step") and self._step_call:
+            # the whole evaluation as ONE library call: repack | one persistent launch for all sets | one reduction (+ Adam); a traction set
+            # takes one of the four slots of the one-stream part's set table (at most three value-only sets beside it)
             x, y, t = self._rows(idx_start, idx_end)
             fold = adam is not None and not self._reduce
+            kw = {} if trac is None else {"traction": trac}
             eng.wave_step(self.theta, x, y, t, self.lb, self.ub, self.normalize, tw, side, grad, sums[0:8], self.E, self.mu, self.rho, True,
-                          adam=(self.adam_m, self.adam_v, adam[0], adam[1]) if fold else None)
+                          adam=(self.adam_m, self.adam_v, adam[0], adam[1]) if fold else None, **kw)
             stepped = fold
         else:
             wrote = False
@@ -289,6 +323,10 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
                 wrote = True
             for i in range(0, len(side), 4):           # all value-only sets of the step in one call (up to PINN_MAX_SETS per call)
                 eng.data_loss_grad_multi(self.theta, side[i:i + 4], self.lb, self.ub, self.normalize, grad_out=grad, accumulate=wrote, packed=wrote)
+                wrote = True
+            if trac is not None:                       # (Adam never runs before this gradient is in: the caller's adam_step follows)
+                eng.wave_traction_loss_grad(self.theta, trac[0], trac[1], trac[2], self.lb, self.ub, self.normalize, trac[3], trac[4],
+                                            grad_out=grad, accumulate=wrote, loss_out=trac[5], packed=wrote)
                 wrote = True
             if not wrote:
                 grad.zero_()
@@ -306,7 +344,10 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
     def train(self, iter, learning_rate, batch_num, record="pre", refine=None, validate=None, identify=None, causal=None):
         """Adam loop of INF:282-319: contiguous collocation blocks, ``iter`` steps per block, all
         side sets fed whole to every block.  Returns the per-step lists
-        (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss).  ``record="pre"`` (default): each recorded value is the loss
+        (loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss); with a traction set (TRAC=...) its per-step term is appended to ``self.trac_rec``, and with at
+        most three value-only sets beside it the step is still ONE library call: the set rides in the step launch's one-stream part
+        (pinn_wave2d_step_traction) -- measured on an MI355X at 8x64, f16x3, 2 M collocation + IC 10 201 + SRC 70 400 points: 4.376 ms per
+        step without the set, 4.389 ms with 20 000 traction points, 4.522 ms with step_call=False (profiles/wave_traction_calls.txt).  ``record="pre"`` (default): each recorded value is the loss
         the step's gradient was taken at -- free.  ``record="post"``: the reference's own bookkeeping, every term re-evaluated
         AFTER the update (its four to six extra sess.run calls per step, INF:308-317) -- one more loss+gradient evaluation per step.
         ``refine``: None, or dict(every, candidates, n_replace, ...) -- refine_collocation with that many device-drawn candidates behind every
@@ -341,7 +382,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
         for i in range(batch_num):
             idx_start = int(i * col_num / batch_num)
             idx_end = int((i + 1) * col_num / batch_num)
-            rec = torch.zeros((iter, 8 * len(_SLOTS)), dtype=torch.float32, device=self.device)
+            rec = torch.zeros((iter, 8 * len(self.SLOTS)), dtype=torch.float32, device=self.device)
 
             def probe():
                 self._loss_and_grad(idx_start, idx_end)
@@ -363,7 +404,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
                     self._loss_and_grad(idx_start, idx_end)
                     rec[it].copy_(self._buf[P:])
                 if self.verbose and it % 10 == 0 and self.rank == 0:
-                    tm = self._terms_from_sums(rec[it].detach().cpu().numpy().reshape(len(_SLOTS), 8), idx_end - idx_start)
+                    tm = self._terms_from_sums(rec[it].detach().cpu().numpy().reshape(len(self.SLOTS), 8), idx_end - idx_start)
                     print('It: %d, Loss: %.3e' % (it, tm["loss"]))
                 if sched is not None or vsched is not None or msched is not None or csched is not None:
                     step += 1
@@ -375,7 +416,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
                         sched.after_step(step)
                     if vsched is not None:
                         vsched.after_step(step)
-            sums = rec.detach().cpu().numpy().reshape(iter, len(_SLOTS), 8)
+            sums = rec.detach().cpu().numpy().reshape(iter, len(self.SLOTS), 8)
             if vsched is not None:
                 vsched.flush()
             self._check_collective()                 # (behind the block's one host synchronisation)
@@ -389,6 +430,8 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
                 loss_IC.append(tm["loss_IC"])
                 loss_SRC.append(tm["loss_SRC"])
                 loss.append(tm["loss"])
+                if "loss_TRAC" in tm:
+                    self.trac_rec.append(tm["loss_TRAC"])
         return loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss
 
     def train_bfgs(self, batch_num, options: Optional[dict] = None, backend: str = "scipy"):
@@ -413,7 +456,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
                 return self._buf
 
             result = self._lbfgs_stage(backend, self.engine, self.theta, evaluate,
-                                       lambda sums: self._terms_from_sums(sums.reshape(len(_SLOTS), 8), idx_end - idx_start)["loss"],
+                                       lambda sums: self._terms_from_sums(sums.reshape(len(self.SLOTS), 8), idx_end - idx_start)["loss"],
                                        self._loss_coeffs(idx_end - idx_start), opts)
         return result
 
@@ -443,7 +486,7 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
         """INF:361-376: (loss, loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss_NB) on the full sets."""
         n = self._n_collo
         self._loss_and_grad(0, n)
-        host = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(_SLOTS), 8)
+        host = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(self.SLOTS), 8)
         self._check_collective()
         tm = self._terms_from_sums(host, n)
         if self.layout["NB"] == 0.0 and "NB" in self._sides:
@@ -452,11 +495,20 @@ class DeepHPM(ShardedSetsModel, PredictMixin, material.MaterialMixin):
             self.layout = dict(lay, NB=1.0)
             try:
                 self._loss_and_grad(0, n)
-                h2 = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(_SLOTS), 8)
+                h2 = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(self.SLOTS), 8)
                 tm["loss_NB"] = self._terms_from_sums(h2, n)["loss_NB"]
             finally:
                 self.layout = lay
         return tm["loss"], tm["loss_f_uv"], tm["loss_f_s"], tm["loss_IC"], tm["loss_SRC"], tm["loss_NB"]
+
+    def getloss_dict(self):
+        """Every loss term on the full sets by name: loss, loss_f_uv, loss_f_s and loss_<set> of each slot (loss_TRAC with a traction set); the
+        terms as they enter the total -- a set the layout excludes reads 0 here where getloss re-evaluates loss_NB."""
+        n = self._n_collo
+        self._loss_and_grad(0, n)
+        host = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(self.SLOTS), 8)
+        self._check_collective()
+        return self._terms_from_sums(host, n)
 
 
 class DeepHPMConfined(DeepHPM):
@@ -496,7 +548,7 @@ class DeepHPMConfined(DeepHPM):
         """CONF:453-472: (loss, loss_f_uv, loss_f_s, loss_IC, loss_SRC, loss_FIX) on the full sets."""
         n = self._n_collo
         self._loss_and_grad(0, n)
-        host = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(_SLOTS), 8)
+        host = self._buf[self.n_params:].detach().cpu().numpy().reshape(len(self.SLOTS), 8)
         self._check_collective()
         tm = self._terms_from_sums(host, n)
         return tm["loss"], tm["loss_f_uv"], tm["loss_f_s"], tm["loss_IC"], tm["loss_SRC"], tm["loss_FIX"]

@@ -264,16 +264,38 @@ class HipEngine(LbfgsMixin):
                                       *self._ws_tail())
         return grad_out
 
+    def wave_traction_loss_grad(self, params, x, y, t, lb, ub, normalize, aux, weights, grad_out=None, accumulate=False, loss_out=None, packed=False):
+        """Traction boundary term of the wave family (pinn_wave2d_traction_loss_grad, INF:267-276).  aux: [4, n] = nx, ny, tx, ty per point,
+        the normals used as given; r_x = s11 nx + s12 ny - tx, r_y = s12 nx + s22 ny - ty.  Returns ((sum r_x^2, sum r_y^2), grad) with
+        grad (+)= d/dparams (weights[0] sum r_x^2 + weights[1] sum r_y^2)."""
+        n = self._check(params, (x, y, t))
+        self._chk(aux, 4 * n)
+        grad_out, accumulate, loss_out = self._outs(grad_out, accumulate, loss_out)
+        self.lib.wave2d_traction_loss_grad(*self._net(params, (x, y, t), n, lb, ub, normalize), aux.data_ptr(), weights, loss_out.data_ptr(),
+                                           grad_out.data_ptr(), accumulate, self._mode(packed), *self._ws_tail())
+        return loss_out[:2], grad_out
+
     def wave_step(self, params, x, y, t, lb, ub, normalize, term_weights, sets, grad_out, loss_out, E=2.5, mu=0.25, rho=1.0, plane_strain=True,
-                  accumulate: bool = False, adam=None):
+                  accumulate: bool = False, adam=None, traction=None):
         """One training step's evaluation in one library call (pinn_wave2d_step): the collocation batch (x, y, t) with its seven term weights, the
         value-only ``sets`` (as data_loss_grad_multi: (x, y, t, targets_or_None, out_weights, loss_out)), the gradient of everything into
         ``grad_out`` and -- with ``adam = (m, v, lr, step[, beta1, beta2, eps])`` -- the TF1 Adam update of ``params`` behind it.  For the nets of
         the register-state fused kernel that is repack | one persistent launch | one reduction (+ Adam); for every other net the library makes
-        the separate calls inside: the same bits either way."""
+        the separate calls inside: the same bits either way.
+        ``traction = (x, y, t, aux[4, n], weights[2], loss_out[>= 2])``: a traction boundary set as well (pinn_wave2d_step_traction): it joins
+        the value-only sets' table as set kind 2 -- at most three ``sets`` then --, same launch, same reduction (+ Adam); None: the call above."""
         n = self._check(params, (x, y, t))
         self._chk(grad_out, self.n_params)
         rows = self._set_rows(sets, self.layers[-1])
+        if traction is not None:
+            tx, ty, tt, taux, tw, tlo = traction
+            tn = self._check(params, (tx, ty, tt))
+            self._chk(taux, 4 * tn)
+            assert tlo.is_cuda and tlo.dtype == torch.float32 and tlo.is_contiguous() and tlo.numel() >= 2
+            self.lib.wave2d_step_traction(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, term_weights, loss_out.data_ptr(),
+                                          rows, tx.data_ptr(), ty.data_ptr(), tt.data_ptr(), tn, taux.data_ptr(), tw, tlo.data_ptr(), grad_out.data_ptr(),
+                                          accumulate, self._adam(adam), self._mode(False), *self._ws_tail())
+            return grad_out
         self.lib.wave2d_step(*self._net(params, (x, y, t), n, lb, ub, normalize), E, mu, rho, plane_strain, term_weights, loss_out.data_ptr(), rows,
                              grad_out.data_ptr(), accumulate, self._adam(adam), self._mode(False), *self._ws_tail())
         return grad_out

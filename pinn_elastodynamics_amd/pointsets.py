@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 
 __all__ = ["lhs", "CartGrid", "GenCirclePT", "GenHoleSurfPT", "DelSrcPT", "DelHolePT", "GenDistPt", "GenDist", "ricker", "gauss_pulse",
-           "source_set", "shuffle", "relative_l2", "preprocess", "probe_points", "frame_times", "infinite_case", "semi_infinite_case",
+           "source_set", "traction_set", "circle_traction_set", "shuffle", "relative_l2", "preprocess", "probe_points", "frame_times", "infinite_case", "semi_infinite_case",
            "confined_case", "plate_case"]
 
 
@@ -115,6 +115,33 @@ def source_set(xc, yc, r, N_PT, times, amplitude=ricker):
     x, y, t = np.tile(xx[:, 0], times.size), np.tile(yy[:, 0], times.size), np.repeat(times, N_PT)
     a = amplitude(t)
     return np.stack([x, y, t, a * (x - xc) / r, a * (y - yc) / r], axis=1)
+
+
+def traction_set(points, normals, times, traction=None):
+    """``TRAC[n, 7] = (x, y, t, nx, ny, tx, ty)`` of an arbitrary boundary for ``DeepHPM(TRAC=...)``: the boundary ``points`` [m, 2] with
+    their ``normals`` [m, 2] at every one of ``times`` (time slowest, as source_set).  The normals are taken as given -- unit vectors pointing
+    out of the solid for a plain mean of squares, or scaled by quadrature weights (the loss term uses them unnormalised).  ``traction``:
+    None (traction-free, zero targets) or a callable (x, y, t) -> (tx, ty) of the prescribed load, arrays of the rows' length."""
+    P, N = np.asarray(points, dtype=np.float64).reshape(-1, 2), np.asarray(normals, dtype=np.float64).reshape(-1, 2)
+    if P.shape != N.shape:
+        raise ValueError("points and normals are both [m, 2]")
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    m = P.shape[0]
+    x, y, t = np.tile(P[:, 0], times.size), np.tile(P[:, 1], times.size), np.repeat(times, m)
+    nx, ny = np.tile(N[:, 0], times.size), np.tile(N[:, 1], times.size)
+    if traction is None:
+        tx, ty = np.zeros_like(x), np.zeros_like(x)
+    else:
+        tx, ty = (np.broadcast_to(np.asarray(v, dtype=np.float64), x.shape) for v in traction(x, y, t))
+    return np.stack([x, y, t, nx, ny, tx, ty], axis=1)
+
+
+def circle_traction_set(xc, yc, r, n_theta, t0, t1, n_time, traction=None):
+    """traction_set for a circular cavity of radius ``r`` about (xc, yc): ``n_theta`` points on the circle (end point excluded, so no point
+    counts twice) at ``n_time`` instants of [t0, t1], unit normals pointing OUT OF THE SOLID, that is into the cavity: -(x - xc, y - yc) / r."""
+    theta = np.linspace(0.0, 2.0 * np.pi, int(n_theta), endpoint=False)
+    c, s_ = np.cos(theta), np.sin(theta)
+    return traction_set(np.stack([xc + r * c, yc + r * s_], 1), np.stack([-c, -s_], 1), np.linspace(t0, t1, int(n_time)), traction)
 
 
 def shuffle(rng, *arrays):
