@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "pinn_heads.hpp"
 
 namespace pinn {
 
@@ -227,6 +228,9 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
     const u32x4* frags;        // fragment store, see frag_index()
 };
 
+// A family's residuals and adjoint seeds are defined once, in pinn_heads.hpp; the loss, score and material heads of the family call them,
+// here and in pinn_fp32.hpp and pinn_fused.hpp (that header names the few sites that stay written out, and why).  A new head of a family
+// is one function there and one call per kernel.
 // HEAD_WAVE   : 4 streams, residuals of net_f_sig (INF:221-265)
 // HEAD_DATA   : 1 stream, sum_o w_o (Y_o - target_o)^2 (INF:111-118)
 // HEAD_FIELDS : forward only, writes all NS streams of the outputs
@@ -252,7 +256,7 @@ struct PackedWeights {         // produced by repack_kernel, consumed by chain_k
 //               (The 4-input family has no such head: value + x, y, z are four streams, and the four-stream instantiations of padded width 128
 //               -- HEAD_SCORE's too -- spill registers where the five-stream ones fit, so at the 10 x 128 net it measured slower than
 //               HEAD_FIELDS3D: 4.83 against 4.64 ms per 1 M points.)
-// HEAD_MATERIAL: forward only, 4 streams: the wave residuals once more, reduced to MATERIAL_SUMS fp64 sums over the points -- the seven sums of
+// HEAD_MATERIAL: forward only, 4 streams: the wave residuals, reduced to MATERIAL_SUMS fp64 sums over the points -- the seven sums of
 //               squares and the seven moment sums the derivatives of the collocation loss by (c1, c2, G, rho) are made of, the residuals being
 //               linear in those four (pinn_wave2d_material_sums).  One record of MATERIAL_SUMS doubles per wave through `moment_part`; a second
 //               launch (pinn_material.hpp) adds the records in index order.  No weights, no per-point output.
@@ -842,21 +846,12 @@ struct Chain {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 const float vm = valid[nb] ? 1.0f : 0.0f;
+                // the family's formulas are in pinn_heads.hpp; here: the mask, the term weights, and where the squares go
+                const auto Yf = [&](int s, int o) { return Y[s][nb][o]; };
+                const auto adjf = [&](int s, int o) -> float& { return adj[s][nb][o]; };
                 if constexpr (HEAD == HEAD_WAVE) {
-                    // net_f_sig INF:221-265; outputs (u,v,ut,vt,s11,s22,s12); streams (value, d/dx, d/dy, d/dt)
-                    const float(&V)[8] = Y[0][nb];
-                    const float(&X)[8] = Y[1][nb];
-                    const float(&Yy)[8] = Y[2][nb];
-                    const float(&T)[8] = Y[3][nb];
-                    const float e11 = X[0], e22 = Yy[1], e12 = Yy[0] + X[1];          // INF:216-218
                     float f[7];
-                    f[0] = X[4] + Yy[6] - a.rho * T[2];                               // f_u   INF:262
-                    f[1] = Yy[5] + X[6] - a.rho * T[3];                               // f_v   INF:263
-                    f[2] = T[0] - V[2];                                               // f_ut  INF:248
-                    f[3] = T[1] - V[3];                                               // f_vt  INF:249
-                    f[4] = V[4] - (a.c1 * e11 + a.c2 * e22);                          // f_s11 INF:244
-                    f[5] = V[5] - (a.c2 * e11 + a.c1 * e22);                          // f_s22 INF:246
-                    f[6] = V[6] - a.G * e12;                                          // f_s12 INF:245
+                    heads::wave_residuals(a, Yf, f);
                     float g[7];
 #pragma unroll
                     for (int i = 0; i < 7; ++i) {
@@ -867,46 +862,10 @@ struct Chain {
                     for (int s = 0; s < NS; ++s)
 #pragma unroll
                         for (int o = 0; o < 8; ++o) adj[s][nb][o] = 0.0f;
-                    adj[0][nb][2] = -g[2];
-                    adj[0][nb][3] = -g[3];
-                    adj[0][nb][4] = g[4];
-                    adj[0][nb][5] = g[5];
-                    adj[0][nb][6] = g[6];
-                    adj[1][nb][0] = -a.c1 * g[4] - a.c2 * g[5];
-                    adj[1][nb][1] = -a.G * g[6];
-                    adj[1][nb][4] = g[0];
-                    adj[1][nb][6] = g[1];
-                    adj[2][nb][0] = -a.G * g[6];
-                    adj[2][nb][1] = -a.c2 * g[4] - a.c1 * g[5];
-                    adj[2][nb][5] = g[1];
-                    adj[2][nb][6] = g[0];
-                    adj[3][nb][0] = g[2];
-                    adj[3][nb][1] = g[3];
-                    adj[3][nb][2] = -a.rho * g[0];
-                    adj[3][nb][3] = -a.rho * g[1];
+                    heads::wave_seeds(a, g, adjf);
                 } else if constexpr (HEAD == HEAD_NC3D) {
-                    // 3-D Navier-Cauchy residuals (oracle/nc3d_oracle.py: the 3-D statement of INF:221-265); outputs
-                    // (u,v,w, ut,vt,wt, s11,s22,s33, s12,s13,s23); streams (value, d/dx, d/dy, d/dz, d/dt); c1 = lambda+2G, c2 = lambda
-                    const float(&V)[16] = Y[0][nb];
-                    const float(&X)[16] = Y[1][nb];
-                    const float(&Yy)[16] = Y[2][nb];
-                    const float(&Zz)[16] = Y[3][nb];
-                    const float(&T)[16] = Y[4][nb];
-                    const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
-                    const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
                     float f[12];
-                    f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
-                    f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
-                    f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
-                    f[3] = T[0] - V[3];
-                    f[4] = T[1] - V[4];
-                    f[5] = T[2] - V[5];
-                    f[6] = V[6] - (a.c1 * e11 + a.c2 * (e22 + e33));
-                    f[7] = V[7] - (a.c1 * e22 + a.c2 * (e11 + e33));
-                    f[8] = V[8] - (a.c1 * e33 + a.c2 * (e11 + e22));
-                    f[9] = V[9] - a.G * e12;
-                    f[10] = V[10] - a.G * e13;
-                    f[11] = V[11] - a.G * e23;
+                    heads::nc3d_residuals(a, Yf, f);
                     float g[12];
 #pragma unroll
                     for (int i = 0; i < 12; ++i) {
@@ -917,41 +876,9 @@ struct Chain {
                     for (int s = 0; s < NS; ++s)
 #pragma unroll
                         for (int o = 0; o < NOG; ++o) adj[s][nb][o] = 0.0f;
-                    // value stream
-                    adj[0][nb][3] = -g[3];
-                    adj[0][nb][4] = -g[4];
-                    adj[0][nb][5] = -g[5];
-#pragma unroll
-                    for (int i = 6; i < 12; ++i) adj[0][nb][i] = g[i];
-                    // d/dx
-                    adj[1][nb][0] = -(a.c1 * g[6] + a.c2 * (g[7] + g[8]));
-                    adj[1][nb][1] = -a.G * g[9];
-                    adj[1][nb][2] = -a.G * g[10];
-                    adj[1][nb][6] = g[0];
-                    adj[1][nb][9] = g[1];
-                    adj[1][nb][10] = g[2];
-                    // d/dy
-                    adj[2][nb][0] = -a.G * g[9];
-                    adj[2][nb][1] = -(a.c1 * g[7] + a.c2 * (g[6] + g[8]));
-                    adj[2][nb][2] = -a.G * g[11];
-                    adj[2][nb][9] = g[0];
-                    adj[2][nb][7] = g[1];
-                    adj[2][nb][11] = g[2];
-                    // d/dz
-                    adj[3][nb][0] = -a.G * g[10];
-                    adj[3][nb][1] = -a.G * g[11];
-                    adj[3][nb][2] = -(a.c1 * g[8] + a.c2 * (g[6] + g[7]));
-                    adj[3][nb][10] = g[0];
-                    adj[3][nb][11] = g[1];
-                    adj[3][nb][8] = g[2];
-                    // d/dt
-                    adj[4][nb][0] = g[3];
-                    adj[4][nb][1] = g[4];
-                    adj[4][nb][2] = g[5];
-                    adj[4][nb][3] = -a.rho * g[0];
-                    adj[4][nb][4] = -a.rho * g[1];
-                    adj[4][nb][5] = -a.rho * g[2];
+                    heads::nc3d_seeds(a, g, adjf);
                 } else if constexpr (HEAD == HEAD_PLATE) {
+                    // (written out: through heads::plate_* the two-kernel plate chain's registers moved, profiles/heads_single_source_isa.txt)
                     // composite F = P + D*N (PLATE:383-387) with product-rule derivatives, then net_f_sig PLATE:404-439
                     // outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt); aux = [D|P][stream][field][n]
                     float D[5][5], F[5][5];
@@ -1014,15 +941,15 @@ struct Chain {
                         adj[4][nb][o] = Fb[4][o] * D[0][o];
                     }
                 } else if constexpr (HEAD == HEAD_TRACTION) {
-                    // net_t PLATE:452-461 on the composite values; aux rows: D0[0..4], P0[5..9], nx[10], ny[11]
-                    float Fv[5], D0[5];
+                    // aux rows: D0[0..4], P0[5..9], nx[10], ny[11]
+                    float D0[5], P0[5], tx, ty;
 #pragma unroll
                     for (int o = 0; o < 5; ++o) {
                         D0[o] = a.aux[(long)o * a.n + pidx[nb]];
-                        Fv[o] = a.aux[(long)(5 + o) * a.n + pidx[nb]] + D0[o] * Y[0][nb][o];
+                        P0[o] = a.aux[(long)(5 + o) * a.n + pidx[nb]];
                     }
                     const float nx = a.aux[10L * a.n + pidx[nb]], ny = a.aux[11L * a.n + pidx[nb]];
-                    const float tx = Fv[2] * nx + Fv[4] * ny, ty = Fv[4] * nx + Fv[3] * ny;
+                    heads::plate_traction_residual(Yf, D0, P0, nx, ny, tx, ty);
                     if (q == 0) {
                         lsum[0] += vm * tx * tx;
                         lsum[1] += vm * ty * ty;
@@ -1030,15 +957,14 @@ struct Chain {
                     const float gx = 2.0f * a.tw[0] * tx * vm, gy = 2.0f * a.tw[1] * ty * vm;
 #pragma unroll
                     for (int o = 0; o < 8; ++o) adj[0][nb][o] = 0.0f;
-                    adj[0][nb][2] = gx * nx * D0[2];
-                    adj[0][nb][3] = gy * ny * D0[3];
-                    adj[0][nb][4] = (gx * ny + gy * nx) * D0[4];
+                    heads::plate_traction_seeds(gx, gy, nx, ny, D0, adjf);
                 } else if constexpr (HEAD == HEAD_TRACTION_WAVE) {
-                    // net_surf_var INF:267-276 on the net's own stresses (outputs u, v, ut, vt, s11, s22, s12), less the prescribed traction;
                     // aux rows: nx[0], ny[1], tx[2], ty[3].  The normals are used as given (not normalised).
                     const float nx = a.aux[0L * a.n + pidx[nb]], ny = a.aux[1L * a.n + pidx[nb]];
-                    const float rx = Y[0][nb][4] * nx + Y[0][nb][6] * ny - a.aux[2L * a.n + pidx[nb]];
-                    const float ry = Y[0][nb][6] * nx + Y[0][nb][5] * ny - a.aux[3L * a.n + pidx[nb]];
+                    float tx, ty;
+                    heads::wave_traction(Yf, nx, ny, tx, ty);
+                    const float rx = tx - a.aux[2L * a.n + pidx[nb]];
+                    const float ry = ty - a.aux[3L * a.n + pidx[nb]];
                     if (q == 0) {
                         lsum[0] += vm * rx * rx;
                         lsum[1] += vm * ry * ry;
@@ -1046,9 +972,7 @@ struct Chain {
                     const float gx = 2.0f * a.tw[0] * rx * vm, gy = 2.0f * a.tw[1] * ry * vm;
 #pragma unroll
                     for (int o = 0; o < 8; ++o) adj[0][nb][o] = 0.0f;
-                    adj[0][nb][4] = gx * nx;
-                    adj[0][nb][5] = gy * ny;
-                    adj[0][nb][6] = gx * ny + gy * nx;
+                    heads::wave_traction_seeds(gx, gy, nx, ny, adjf);
                 } else if constexpr (HEAD == HEAD_STREAMS) {
                     // sum_{s,o} w[s][o] (Y[s][o] - target[s][o])^2 ; lsum[o] accumulates the weight-normalised sum over streams
 #pragma unroll
@@ -1071,42 +995,19 @@ struct Chain {
                         adj[0][nb][o] = 2.0f * a.tw[o] * d * vm;
                     }
                 } else if constexpr (HEAD == HEAD_SCORE) {
-                    // per-point residual measure sum_i tw[i] f_i^2 from the streams at hand.  The seven lines are HEAD_WAVE's (net_f_sig
-                    // INF:221-265), kept as a second copy so that the loss kernels' code does not move; nothing is differentiated here.
-                    const float(&V)[8] = Y[0][nb];
-                    const float(&X)[8] = Y[1][nb];
-                    const float(&Yy)[8] = Y[2][nb];
-                    const float(&T)[8] = Y[3][nb];
-                    const float e11 = X[0], e22 = Yy[1], e12 = Yy[0] + X[1];          // INF:216-218
+                    // per-point residual measure sum_i tw[i] f_i^2 of HEAD_WAVE's residuals from the streams at hand; nothing is differentiated
                     float f[7];
-                    f[0] = X[4] + Yy[6] - a.rho * T[2];                               // f_u   INF:262
-                    f[1] = Yy[5] + X[6] - a.rho * T[3];                               // f_v   INF:263
-                    f[2] = T[0] - V[2];                                               // f_ut  INF:248
-                    f[3] = T[1] - V[3];                                               // f_vt  INF:249
-                    f[4] = V[4] - (a.c1 * e11 + a.c2 * e22);                          // f_s11 INF:244
-                    f[5] = V[5] - (a.c2 * e11 + a.c1 * e22);                          // f_s22 INF:246
-                    f[6] = V[6] - a.G * e12;                                          // f_s12 INF:245
+                    heads::wave_residuals(a, Yf, f);
                     float sc = 0.0f;
 #pragma unroll
                     for (int i = 0; i < 7; ++i) sc += a.tw[i] * (f[i] * f[i]);
                     if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
                 } else if constexpr (HEAD == HEAD_MATERIAL) {
-                    // the seven residuals once more (a third copy of HEAD_WAVE's lines, net_f_sig INF:221-265: the loss kernels' code does not
-                    // move), formed in fp32; their squares and their products with the strain / acceleration streams they are linear in are
-                    // exact in fp64 and added per lane.  A padded lane (valid[nb] false: it re-read point n - 1) adds nothing.
-                    const float(&V)[8] = Y[0][nb];
-                    const float(&X)[8] = Y[1][nb];
-                    const float(&Yy)[8] = Y[2][nb];
-                    const float(&T)[8] = Y[3][nb];
-                    const float e11 = X[0], e22 = Yy[1], e12 = Yy[0] + X[1];          // INF:216-218
+                    // HEAD_WAVE's residuals, formed in fp32; their squares and their products with the strain / acceleration streams they are
+                    // linear in are exact in fp64 and added per lane.  A padded lane (valid[nb] false: it re-read point n - 1) adds nothing.
                     float f[7];
-                    f[0] = X[4] + Yy[6] - a.rho * T[2];                               // f_u   INF:262
-                    f[1] = Yy[5] + X[6] - a.rho * T[3];                               // f_v   INF:263
-                    f[2] = T[0] - V[2];                                               // f_ut  INF:248
-                    f[3] = T[1] - V[3];                                               // f_vt  INF:249
-                    f[4] = V[4] - (a.c1 * e11 + a.c2 * e22);                          // f_s11 INF:244
-                    f[5] = V[5] - (a.c2 * e11 + a.c1 * e22);                          // f_s22 INF:246
-                    f[6] = V[6] - a.G * e12;                                          // f_s12 INF:245
+                    const heads::Strains2 e = heads::wave_strains(Yf);
+                    heads::wave_residuals(a, Yf, f);
                     if (q == 0 && valid[nb]) {
                         double fd[7];
 #pragma unroll
@@ -1114,42 +1015,29 @@ struct Chain {
                             fd[i] = (double)f[i];
                             msum[i] += fd[i] * fd[i];
                         }
-                        const double d11 = (double)e11, d22 = (double)e22;
+                        const double d11 = (double)e.e11, d22 = (double)e.e22;
                         msum[7] += fd[4] * d11;
                         msum[8] += fd[4] * d22;
                         msum[9] += fd[5] * d11;
                         msum[10] += fd[5] * d22;
-                        msum[11] += fd[6] * (double)e12;
-                        msum[12] += fd[0] * (double)T[2];
-                        msum[13] += fd[1] * (double)T[3];
+                        msum[11] += fd[6] * (double)e.e12;
+                        msum[12] += fd[0] * (double)Y[3][nb][2];
+                        msum[13] += fd[1] * (double)Y[3][nb][3];
                     }
                 } else if constexpr (HEAD == HEAD_MATERIAL_PLATE) {
-                    // the plate's sums: composite F = P + D*N and the five residuals exactly as HEAD_SCORE_PLATE forms them (PLATE:383-387,
-                    // 404-439), a third copy, in fp32; squares and products with the composite's strains / accelerations in fp64 per lane.
-                    // A padded lane adds nothing.
-                    float D[5][5], F[5][5];
+                    // the plate's sums: HEAD_PLATE's composite and residuals in fp32; squares and products with the composite's strains /
+                    // accelerations in fp64 per lane.  A padded lane adds nothing.
+                    float D[5][5], F[5][5], f[5];      // the point's frozen streams, aux = [D|P][stream][field][n]; F starts from P
 #pragma unroll
                     for (int st = 0; st < 5; ++st)
 #pragma unroll
                         for (int o = 0; o < 5; ++o) {
                             D[st][o] = a.aux[((long)(0 * 5 + st) * 5 + o) * a.n + pidx[nb]];
-                            F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + pidx[nb]];      // start from P
+                            F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + pidx[nb]];
                         }
-#pragma unroll
-                    for (int o = 0; o < 5; ++o) {
-                        const float n0 = Y[0][nb][o];
-                        F[0][o] += D[0][o] * n0;
-#pragma unroll
-                        for (int k = 1; k <= 3; ++k) F[k][o] += D[k][o] * n0 + D[0][o] * Y[k][nb][o];
-                        F[4][o] += D[4][o] * n0 + 2.0f * D[3][o] * Y[3][nb][o] + D[0][o] * Y[4][nb][o];
-                    }
-                    const float e11 = F[1][0], e22 = F[2][1], e12 = F[2][0] + F[1][1];
-                    float f[5];
-                    f[0] = F[1][2] + F[2][4] - a.rho * F[4][0];                       // f_u   PLATE:436
-                    f[1] = F[2][3] + F[1][4] - a.rho * F[4][1];                       // f_v   PLATE:437
-                    f[2] = F[0][2] - (a.c1 * e11 + a.c2 * e22);                       // f_s11 PLATE:421
-                    f[3] = F[0][3] - (a.c2 * e11 + a.c1 * e22);                       // f_s22 PLATE:423
-                    f[4] = F[0][4] - a.G * e12;                                       // f_s12 PLATE:422
+                    heads::plate_composite(Yf, D, F);
+                    const heads::Strains2 e = heads::plate_strains(F);
+                    heads::plate_residuals(a, F, f);
                     if (q == 0 && valid[nb]) {
                         double fd[5];
 #pragma unroll
@@ -1157,17 +1045,18 @@ struct Chain {
                             fd[i] = (double)f[i];
                             msum[i] += fd[i] * fd[i];
                         }
-                        const double d11 = (double)e11, d22 = (double)e22;
+                        const double d11 = (double)e.e11, d22 = (double)e.e22;
                         msum[5] += fd[2] * d11;
                         msum[6] += fd[2] * d22;
                         msum[7] += fd[3] * d11;
                         msum[8] += fd[3] * d22;
-                        msum[9] += fd[4] * (double)e12;
+                        msum[9] += fd[4] * (double)e.e12;
                         msum[10] += fd[0] * (double)F[4][0];
                         msum[11] += fd[1] * (double)F[4][1];
                     }
                 } else if constexpr (HEAD == HEAD_MATERIAL3D) {
-                    // the 3-D sums: the twelve residuals of HEAD_SCORE3D (oracle/nc3d_oracle.py), a third copy, in fp32; the pair sums of the
+                    // (written out: through heads::nc3d_residuals this head's spills moved, profiles/heads_single_source_isa.txt)
+                    // the 3-D sums: the twelve residuals of HEAD_SCORE3D (oracle/nc3d_oracle.py), in fp32; the pair sums of the
                     // normal strains are single fp32 additions, widened for the product only.  A padded lane adds nothing.
                     const float(&V)[16] = Y[0][nb];
                     const float(&X)[16] = Y[1][nb];
@@ -1211,58 +1100,25 @@ struct Chain {
                         msum[23] += fd[2] * (double)T[5];
                     }
                 } else if constexpr (HEAD == HEAD_SCORE_PLATE) {
-                    // the plate's score: composite F = P + D*N and the five residuals exactly as HEAD_PLATE forms them (PLATE:383-387,
-                    // 404-439), a second copy like HEAD_SCORE's; outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt)
-                    float D[5][5], F[5][5];
+                    // the plate's score: HEAD_PLATE's composite and its five residuals
+                    float D[5][5], F[5][5], f[5];      // the point's frozen streams, aux = [D|P][stream][field][n]; F starts from P
 #pragma unroll
                     for (int st = 0; st < 5; ++st)
 #pragma unroll
                         for (int o = 0; o < 5; ++o) {
                             D[st][o] = a.aux[((long)(0 * 5 + st) * 5 + o) * a.n + pidx[nb]];
-                            F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + pidx[nb]];      // start from P
+                            F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + pidx[nb]];
                         }
-#pragma unroll
-                    for (int o = 0; o < 5; ++o) {
-                        const float n0 = Y[0][nb][o];
-                        F[0][o] += D[0][o] * n0;
-#pragma unroll
-                        for (int k = 1; k <= 3; ++k) F[k][o] += D[k][o] * n0 + D[0][o] * Y[k][nb][o];
-                        F[4][o] += D[4][o] * n0 + 2.0f * D[3][o] * Y[3][nb][o] + D[0][o] * Y[4][nb][o];
-                    }
-                    const float e11 = F[1][0], e22 = F[2][1], e12 = F[2][0] + F[1][1];
-                    float f[5];
-                    f[0] = F[1][2] + F[2][4] - a.rho * F[4][0];                       // f_u   PLATE:436
-                    f[1] = F[2][3] + F[1][4] - a.rho * F[4][1];                       // f_v   PLATE:437
-                    f[2] = F[0][2] - (a.c1 * e11 + a.c2 * e22);                       // f_s11 PLATE:421
-                    f[3] = F[0][3] - (a.c2 * e11 + a.c1 * e22);                       // f_s22 PLATE:423
-                    f[4] = F[0][4] - a.G * e12;                                       // f_s12 PLATE:422
+                    heads::plate_composite(Yf, D, F);
+                    heads::plate_residuals(a, F, f);
                     float sc = 0.0f;
 #pragma unroll
                     for (int i = 0; i < 5; ++i) sc += a.tw[i] * (f[i] * f[i]);
                     if (q == 0 && valid[nb]) a.fields_out[pidx[nb]] = sc;
                 } else if constexpr (HEAD == HEAD_SCORE3D) {
-                    // the 3-D score: the twelve residuals of HEAD_NC3D (oracle/nc3d_oracle.py), a second copy; outputs
-                    // (u,v,w, ut,vt,wt, s11,s22,s33, s12,s13,s23); streams (value, d/dx, d/dy, d/dz, d/dt); c1 = lambda+2G, c2 = lambda
-                    const float(&V)[16] = Y[0][nb];
-                    const float(&X)[16] = Y[1][nb];
-                    const float(&Yy)[16] = Y[2][nb];
-                    const float(&Zz)[16] = Y[3][nb];
-                    const float(&T)[16] = Y[4][nb];
-                    const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
-                    const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
+                    // the 3-D score: HEAD_NC3D's twelve residuals
                     float f[12];
-                    f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
-                    f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
-                    f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
-                    f[3] = T[0] - V[3];
-                    f[4] = T[1] - V[4];
-                    f[5] = T[2] - V[5];
-                    f[6] = V[6] - (a.c1 * e11 + a.c2 * (e22 + e33));
-                    f[7] = V[7] - (a.c1 * e22 + a.c2 * (e11 + e33));
-                    f[8] = V[8] - (a.c1 * e33 + a.c2 * (e11 + e22));
-                    f[9] = V[9] - a.G * e12;
-                    f[10] = V[10] - a.G * e13;
-                    f[11] = V[11] - a.G * e23;
+                    heads::nc3d_residuals(a, Yf, f);
                     float sc = 0.0f;
 #pragma unroll
                     for (int i = 0; i < 12; ++i) sc += a.tw[i] * (f[i] * f[i]);

@@ -145,40 +145,32 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             o[7 * a.n] = Fk[1][0] + Fk[0][1];
             continue;
         }
+        // The families' residuals and seeds are in pinn_heads.hpp; the heads below decide where the squares go.  The plate's four heads
+        // (HEAD_PLATE, HEAD_SCORE_PLATE, HEAD_MATERIAL_PLATE, HEAD_TRACTION) are written out here: inside heads::plate_* the compiler for
+        // gfx950 contracts their expressions into other fused multiply-adds, and the outputs change in the last bits
+        // (profiles/heads_single_source_ab.txt).
+        const auto Yf = [&](int s, int o) { return Y[s][o]; };
         if (a.head == HEAD_SCORE) {
-            // pinn_wave2d_residual_score: sum_i tw[i] f_i^2 of the wave residuals (the lines of HEAD_WAVE below), one float per point through fields_out
-            const float e11 = Y[1][0], e22 = Y[2][1], e12 = Y[2][0] + Y[1][1];
+            // pinn_wave2d_residual_score: sum_i tw[i] f_i^2 of the wave residuals, one float per point through fields_out
             float f[7];
-            f[0] = Y[1][4] + Y[2][6] - a.rho * Y[3][2];
-            f[1] = Y[2][5] + Y[1][6] - a.rho * Y[3][3];
-            f[2] = Y[3][0] - Y[0][2];
-            f[3] = Y[3][1] - Y[0][3];
-            f[4] = Y[0][4] - (a.c1 * e11 + a.c2 * e22);
-            f[5] = Y[0][5] - (a.c2 * e11 + a.c1 * e22);
-            f[6] = Y[0][6] - a.G * e12;
+            heads::wave_residuals(a, Yf, f);
             float sc = 0.0f;
             for (int i = 0; i < 7; ++i) sc += a.tw[i] * (f[i] * f[i]);
             a.fields_out[gp] = sc;
             continue;
         }
         if (a.head == HEAD_MATERIAL) {
-            // pinn_wave2d_material_sums: the seven residuals (the lines of HEAD_WAVE below), their squares and their products with the streams
-            // they are linear in, one fp32 row each of the pass's `fsq` buffer; material::fp32_partial_kernel adds the rows in fp64
-            const float e11 = Y[1][0], e22 = Y[2][1], e12 = Y[2][0] + Y[1][1];
+            // pinn_wave2d_material_sums: the seven wave residuals, their squares and their products with the streams they are linear in,
+            // one fp32 row each of the pass's `fsq` buffer; material::fp32_partial_kernel adds the rows in fp64
             float f[7];
-            f[0] = Y[1][4] + Y[2][6] - a.rho * Y[3][2];
-            f[1] = Y[2][5] + Y[1][6] - a.rho * Y[3][3];
-            f[2] = Y[3][0] - Y[0][2];
-            f[3] = Y[3][1] - Y[0][3];
-            f[4] = Y[0][4] - (a.c1 * e11 + a.c2 * e22);
-            f[5] = Y[0][5] - (a.c2 * e11 + a.c1 * e22);
-            f[6] = Y[0][6] - a.G * e12;
+            const heads::Strains2 e = heads::wave_strains(Yf);
+            heads::wave_residuals(a, Yf, f);
             for (int i = 0; i < 7; ++i) a.fsq[(long)i * a.m + p] = f[i] * f[i];
-            a.fsq[7L * a.m + p] = f[4] * e11;
-            a.fsq[8L * a.m + p] = f[4] * e22;
-            a.fsq[9L * a.m + p] = f[5] * e11;
-            a.fsq[10L * a.m + p] = f[5] * e22;
-            a.fsq[11L * a.m + p] = f[6] * e12;
+            a.fsq[7L * a.m + p] = f[4] * e.e11;
+            a.fsq[8L * a.m + p] = f[4] * e.e22;
+            a.fsq[9L * a.m + p] = f[5] * e.e11;
+            a.fsq[10L * a.m + p] = f[5] * e.e22;
+            a.fsq[11L * a.m + p] = f[6] * e.e12;
             a.fsq[12L * a.m + p] = f[0] * Y[3][2];
             a.fsq[13L * a.m + p] = f[1] * Y[3][3];
             continue;
@@ -216,44 +208,27 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             continue;
         }
         if (FAMILY_SUMS && a.head == HEAD_MATERIAL3D) {
-            // pinn_nc3d_material_sums: the twelve residuals of HEAD_NC3D below; this launch leaves the twelve squares (part 0) or the twelve
-            // moments (part 1) in rows 0..11 of `fsq` -- FP32_TERMS rows do not hold all 24
-            const float* V = Y[0];
-            const float* X = Y[1];
-            const float* Yy = Y[2];
-            const float* Zz = Y[3];
-            const float* T = Y[4];
-            const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
-            const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
-            const float p23 = e22 + e33, p13 = e11 + e33, p12 = e11 + e22;
+            // pinn_nc3d_material_sums: the twelve 3-D residuals; this launch leaves the twelve squares (part 0) or the twelve moments
+            // (part 1) in rows 0..11 of `fsq` -- FP32_TERMS rows do not hold all 24
             float f[12];
-            f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
-            f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
-            f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
-            f[3] = T[0] - V[3];
-            f[4] = T[1] - V[4];
-            f[5] = T[2] - V[5];
-            f[6] = V[6] - (a.c1 * e11 + a.c2 * p23);
-            f[7] = V[7] - (a.c1 * e22 + a.c2 * p13);
-            f[8] = V[8] - (a.c1 * e33 + a.c2 * p12);
-            f[9] = V[9] - a.G * e12;
-            f[10] = V[10] - a.G * e13;
-            f[11] = V[11] - a.G * e23;
+            const heads::Strains3 e = heads::nc3d_strains(Yf);
+            const float p23 = e.e22 + e.e33, p13 = e.e11 + e.e33, p12 = e.e11 + e.e22;
+            heads::nc3d_residuals(a, Yf, f);
             if (a.part == 0) {
                 for (int i = 0; i < 12; ++i) a.fsq[(long)i * a.m + p] = f[i] * f[i];
             } else {
-                a.fsq[0L * a.m + p] = f[6] * e11;
+                a.fsq[0L * a.m + p] = f[6] * e.e11;
                 a.fsq[1L * a.m + p] = f[6] * p23;
-                a.fsq[2L * a.m + p] = f[7] * e22;
+                a.fsq[2L * a.m + p] = f[7] * e.e22;
                 a.fsq[3L * a.m + p] = f[7] * p13;
-                a.fsq[4L * a.m + p] = f[8] * e33;
+                a.fsq[4L * a.m + p] = f[8] * e.e33;
                 a.fsq[5L * a.m + p] = f[8] * p12;
-                a.fsq[6L * a.m + p] = f[9] * e12;
-                a.fsq[7L * a.m + p] = f[10] * e13;
-                a.fsq[8L * a.m + p] = f[11] * e23;
-                a.fsq[9L * a.m + p] = f[0] * T[3];
-                a.fsq[10L * a.m + p] = f[1] * T[4];
-                a.fsq[11L * a.m + p] = f[2] * T[5];
+                a.fsq[6L * a.m + p] = f[9] * e.e12;
+                a.fsq[7L * a.m + p] = f[10] * e.e13;
+                a.fsq[8L * a.m + p] = f[11] * e.e23;
+                a.fsq[9L * a.m + p] = f[0] * Y[4][3];
+                a.fsq[10L * a.m + p] = f[1] * Y[4][4];
+                a.fsq[11L * a.m + p] = f[2] * Y[4][5];
             }
             continue;
         }
@@ -284,27 +259,9 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             continue;
         }
         if (a.head == HEAD_SCORE3D) {
-            // pinn_nc3d_residual_score: the twelve residuals of HEAD_NC3D below, sum_i tw[i] f_i^2 through fields_out
-            const float* V = Y[0];
-            const float* X = Y[1];
-            const float* Yy = Y[2];
-            const float* Zz = Y[3];
-            const float* T = Y[4];
-            const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
-            const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
+            // pinn_nc3d_residual_score: the twelve 3-D residuals, sum_i tw[i] f_i^2 through fields_out
             float f[12];
-            f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
-            f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
-            f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
-            f[3] = T[0] - V[3];
-            f[4] = T[1] - V[4];
-            f[5] = T[2] - V[5];
-            f[6] = V[6] - (a.c1 * e11 + a.c2 * (e22 + e33));
-            f[7] = V[7] - (a.c1 * e22 + a.c2 * (e11 + e33));
-            f[8] = V[8] - (a.c1 * e33 + a.c2 * (e11 + e22));
-            f[9] = V[9] - a.G * e12;
-            f[10] = V[10] - a.G * e13;
-            f[11] = V[11] - a.G * e23;
+            heads::nc3d_residuals(a, Yf, f);
             float sc = 0.0f;
             for (int i = 0; i < 12; ++i) sc += a.tw[i] * (f[i] * f[i]);
             a.fields_out[gp] = sc;
@@ -314,95 +271,23 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
         float adj[FP32_MAX_NS][FP32_NOUT];
         for (int s = 0; s < FP32_MAX_NS; ++s)
             for (int o = 0; o < FP32_NOUT; ++o) adj[s][o] = 0.0f;
+        const auto adjf = [&](int s, int o) -> float& { return adj[s][o]; };
         if (a.head == HEAD_WAVE) {
-            // outputs (u,v,ut,vt,s11,s22,s12); streams (value, d/dx, d/dy, d/dt)          net_f_sig INF:221-265
-            const float e11 = Y[1][0], e22 = Y[2][1], e12 = Y[2][0] + Y[1][1];        // INF:216-218
-            float f[7];
-            f[0] = Y[1][4] + Y[2][6] - a.rho * Y[3][2];                               // f_u   INF:262
-            f[1] = Y[2][5] + Y[1][6] - a.rho * Y[3][3];                               // f_v   INF:263
-            f[2] = Y[3][0] - Y[0][2];                                                 // f_ut  INF:248
-            f[3] = Y[3][1] - Y[0][3];                                                 // f_vt  INF:249
-            f[4] = Y[0][4] - (a.c1 * e11 + a.c2 * e22);                               // f_s11 INF:244
-            f[5] = Y[0][5] - (a.c2 * e11 + a.c1 * e22);                               // f_s22 INF:246
-            f[6] = Y[0][6] - a.G * e12;                                               // f_s12 INF:245
-            float g[7];
+            float f[7], g[7];
+            heads::wave_residuals(a, Yf, f);
             for (int i = 0; i < 7; ++i) {
                 a.fsq[(long)i * a.m + p] = f[i] * f[i];
                 g[i] = 2.0f * a.tw[i] * f[i];
             }
-            adj[0][2] = -g[2];
-            adj[0][3] = -g[3];
-            adj[0][4] = g[4];
-            adj[0][5] = g[5];
-            adj[0][6] = g[6];
-            adj[1][0] = -a.c1 * g[4] - a.c2 * g[5];
-            adj[1][1] = -a.G * g[6];
-            adj[1][4] = g[0];
-            adj[1][6] = g[1];
-            adj[2][0] = -a.G * g[6];
-            adj[2][1] = -a.c2 * g[4] - a.c1 * g[5];
-            adj[2][5] = g[1];
-            adj[2][6] = g[0];
-            adj[3][0] = g[2];
-            adj[3][1] = g[3];
-            adj[3][2] = -a.rho * g[0];
-            adj[3][3] = -a.rho * g[1];
+            heads::wave_seeds(a, g, adjf);
         } else if (a.head == HEAD_NC3D) {
-            // outputs (u,v,w, ut,vt,wt, s11,s22,s33, s12,s13,s23); streams (value, d/dx, d/dy, d/dz, d/dt); c1 = lambda + 2G, c2 = lambda
-            // (oracle/nc3d_oracle.py: the 3-D statement of INF:221-265)
-            const float* V = Y[0];
-            const float* X = Y[1];
-            const float* Yy = Y[2];
-            const float* Zz = Y[3];
-            const float* T = Y[4];
-            const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
-            const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
-            float f[12];
-            f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
-            f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
-            f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
-            f[3] = T[0] - V[3];
-            f[4] = T[1] - V[4];
-            f[5] = T[2] - V[5];
-            f[6] = V[6] - (a.c1 * e11 + a.c2 * (e22 + e33));
-            f[7] = V[7] - (a.c1 * e22 + a.c2 * (e11 + e33));
-            f[8] = V[8] - (a.c1 * e33 + a.c2 * (e11 + e22));
-            f[9] = V[9] - a.G * e12;
-            f[10] = V[10] - a.G * e13;
-            f[11] = V[11] - a.G * e23;
-            float g[12];
+            float f[12], g[12];
+            heads::nc3d_residuals(a, Yf, f);
             for (int i = 0; i < 12; ++i) {
                 a.fsq[(long)i * a.m + p] = f[i] * f[i];
                 g[i] = 2.0f * a.tw[i] * f[i];
             }
-            adj[0][3] = -g[3];
-            adj[0][4] = -g[4];
-            adj[0][5] = -g[5];
-            for (int i = 6; i < 12; ++i) adj[0][i] = g[i];
-            adj[1][0] = -(a.c1 * g[6] + a.c2 * (g[7] + g[8]));
-            adj[1][1] = -a.G * g[9];
-            adj[1][2] = -a.G * g[10];
-            adj[1][6] = g[0];
-            adj[1][9] = g[1];
-            adj[1][10] = g[2];
-            adj[2][0] = -a.G * g[9];
-            adj[2][1] = -(a.c1 * g[7] + a.c2 * (g[6] + g[8]));
-            adj[2][2] = -a.G * g[11];
-            adj[2][9] = g[0];
-            adj[2][7] = g[1];
-            adj[2][11] = g[2];
-            adj[3][0] = -a.G * g[10];
-            adj[3][1] = -a.G * g[11];
-            adj[3][2] = -(a.c1 * g[8] + a.c2 * (g[6] + g[7]));
-            adj[3][10] = g[0];
-            adj[3][11] = g[1];
-            adj[3][8] = g[2];
-            adj[4][0] = g[3];
-            adj[4][1] = g[4];
-            adj[4][2] = g[5];
-            adj[4][3] = -a.rho * g[0];
-            adj[4][4] = -a.rho * g[1];
-            adj[4][5] = -a.rho * g[2];
+            heads::nc3d_seeds(a, g, adjf);
         } else if (a.head == HEAD_PLATE) {
             // composite F = P + D*N (PLATE:383-387) with product-rule derivatives, then net_f_sig PLATE:404-439
             // outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt); aux = [D|P][stream][field][n]
@@ -469,17 +354,16 @@ __global__ __launch_bounds__(256) void fp32_chain_kernel(const Fp32Args a) {
             adj[0][3] = gy * ny * D0[3];
             adj[0][4] = (gx * ny + gy * nx) * D0[4];
         } else if (a.head == HEAD_TRACTION_WAVE) {
-            // net_surf_var INF:267-276 on the net's own stresses (outputs 4, 5, 6 = s11, s22, s12), less the prescribed traction;
             // aux rows: nx[0], ny[1], tx[2], ty[3], normals used as given
             const float nx = a.aux[0L * a.n + gp], ny = a.aux[1L * a.n + gp];
-            const float rx = Y[0][4] * nx + Y[0][6] * ny - a.aux[2L * a.n + gp];
-            const float ry = Y[0][6] * nx + Y[0][5] * ny - a.aux[3L * a.n + gp];
+            float tx, ty;
+            heads::wave_traction(Yf, nx, ny, tx, ty);
+            const float rx = tx - a.aux[2L * a.n + gp];
+            const float ry = ty - a.aux[3L * a.n + gp];
             a.fsq[0L * a.m + p] = rx * rx;
             a.fsq[1L * a.m + p] = ry * ry;
             const float gx = 2.0f * a.tw[0] * rx, gy = 2.0f * a.tw[1] * ry;
-            adj[0][4] = gx * nx;
-            adj[0][5] = gy * ny;
-            adj[0][6] = gx * ny + gy * nx;
+            heads::wave_traction_seeds(gx, gy, nx, ny, adjf);
         } else if (a.head == HEAD_STREAMS) {
             // sum_{s,o} w[s][o] (Y[s][o] - target[s][o])^2 : the loss term of output o collects its streams (PLATE:194-215)
             for (int o = 0; o < NO; ++o) {

@@ -2730,64 +2730,19 @@ struct Fused {
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int o = 0; o < NOG; ++o) adj[s][o] = 0.0f;
+        // the family's formulas are in pinn_heads.hpp; here: the mask, the term weights (held in the loop), and the loss sums
+        const auto Yf = [&](int s, int o) { return Y[s][o]; };
+        const auto adjf = [&](int s, int o) -> float& { return adj[s][o]; };
         if constexpr (HEAD == HEAD_NC3D) {
-            // 3-D Navier-Cauchy residuals (oracle/nc3d_oracle.py: the 3-D statement of INF:221-265); outputs (u,v,w, ut,vt,wt, s11,s22,s33,
-            // s12,s13,s23); streams (value, d/dx, d/dy, d/dz, d/dt); c1 = lambda + 2G, c2 = lambda
-            const float(&V)[NOG] = Y[0];
-            const float(&X)[NOG] = Y[1];
-            const float(&Yy)[NOG] = Y[2];
-            const float(&Zz)[NOG] = Y[3];
-            const float(&T)[NOG] = Y[4];
-            const float e11 = X[0], e22 = Yy[1], e33 = Zz[2];
-            const float e12 = Yy[0] + X[1], e13 = Zz[0] + X[2], e23 = Zz[1] + Yy[2];
             float f[12];
-            f[0] = X[6] + Yy[9] + Zz[10] - a.rho * T[3];
-            f[1] = X[9] + Yy[7] + Zz[11] - a.rho * T[4];
-            f[2] = X[10] + Yy[11] + Zz[8] - a.rho * T[5];
-            f[3] = T[0] - V[3];
-            f[4] = T[1] - V[4];
-            f[5] = T[2] - V[5];
-            f[6] = V[6] - (a.c1 * e11 + a.c2 * (e22 + e33));
-            f[7] = V[7] - (a.c1 * e22 + a.c2 * (e11 + e33));
-            f[8] = V[8] - (a.c1 * e33 + a.c2 * (e11 + e22));
-            f[9] = V[9] - a.G * e12;
-            f[10] = V[10] - a.G * e13;
-            f[11] = V[11] - a.G * e23;
+            heads::nc3d_residuals(a, Yf, f);
             float g[12];
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
                 if (q == 0) lsum[i] += vm * f[i] * f[i];
                 g[i] = 2.0f * in_loop(a.tw[i]) * f[i] * vm;
             }
-            adj[0][3] = -g[3];
-            adj[0][4] = -g[4];
-            adj[0][5] = -g[5];
-#pragma unroll
-            for (int i = 6; i < 12; ++i) adj[0][i] = g[i];
-            adj[1][0] = -(a.c1 * g[6] + a.c2 * (g[7] + g[8]));
-            adj[1][1] = -a.G * g[9];
-            adj[1][2] = -a.G * g[10];
-            adj[1][6] = g[0];
-            adj[1][9] = g[1];
-            adj[1][10] = g[2];
-            adj[2][0] = -a.G * g[9];
-            adj[2][1] = -(a.c1 * g[7] + a.c2 * (g[6] + g[8]));
-            adj[2][2] = -a.G * g[11];
-            adj[2][9] = g[0];
-            adj[2][7] = g[1];
-            adj[2][11] = g[2];
-            adj[3][0] = -a.G * g[10];
-            adj[3][1] = -a.G * g[11];
-            adj[3][2] = -(a.c1 * g[8] + a.c2 * (g[6] + g[7]));
-            adj[3][10] = g[0];
-            adj[3][11] = g[1];
-            adj[3][8] = g[2];
-            adj[4][0] = g[3];
-            adj[4][1] = g[4];
-            adj[4][2] = g[5];
-            adj[4][3] = -a.rho * g[0];
-            adj[4][4] = -a.rho * g[1];
-            adj[4][5] = -a.rho * g[2];
+            heads::nc3d_seeds(a, g, adjf);
         } else if constexpr (SSETS) {
             // sum_{s,o} w[s][o] (Y[s][o] - target[s][o])^2 of the step's set (chain_kernel's HEAD_STREAMS, pinn_device.hpp); lsum[o] accumulates the
             // weight-normalised sum over streams.  Only the pairs of the set's mask: a row whose weight is 0 is never read.
@@ -2806,9 +2761,8 @@ struct Fused {
                         adj[s][o] = (WG_HI ? 2.0f * ZDB_SEED_SCALE : 2.0f) * w * d * vm;      // (the seed scale of the fp16 adjoints: taken back at the reduction)
                     }
         } else if constexpr (HEAD == HEAD_PLATE) {
-            // composite F = P + D*N (PLATE:383-387) with product-rule derivatives, then net_f_sig PLATE:404-439
-            // outputs (u,v,s11,s22,s12); streams (value, x, y, t, tt); aux = [D|P][stream][field][n]
-            float D[5][5], F[5][5];
+            // the point's frozen streams, aux = [D|P][stream][field][n]; composite, residuals and seeds: heads::plate_*
+            float D[5][5], F[5][5], f[5];
 #pragma unroll
             for (int st = 0; st < 5; ++st)
 #pragma unroll
@@ -2816,88 +2770,28 @@ struct Fused {
                     D[st][o] = a.aux[((long)(0 * 5 + st) * 5 + o) * a.n + pidx];
                     F[st][o] = a.aux[((long)(1 * 5 + st) * 5 + o) * a.n + pidx];      // start from P
                 }
-#pragma unroll
-            for (int o = 0; o < 5; ++o) {
-                const float n0 = Y[0][o];
-                F[0][o] += D[0][o] * n0;
-#pragma unroll
-                for (int k = 1; k <= 3; ++k) F[k][o] += D[k][o] * n0 + D[0][o] * Y[k][o];
-                F[4][o] += D[4][o] * n0 + 2.0f * D[3][o] * Y[3][o] + D[0][o] * Y[4][o];
-            }
-            const float e11 = F[1][0], e22 = F[2][1], e12 = F[2][0] + F[1][1];
-            float f[5];
-            f[0] = F[1][2] + F[2][4] - a.rho * F[4][0];                       // f_u   PLATE:436
-            f[1] = F[2][3] + F[1][4] - a.rho * F[4][1];                       // f_v   PLATE:437
-            f[2] = F[0][2] - (a.c1 * e11 + a.c2 * e22);                       // f_s11 PLATE:421
-            f[3] = F[0][3] - (a.c2 * e11 + a.c1 * e22);                       // f_s22 PLATE:423
-            f[4] = F[0][4] - a.G * e12;                                       // f_s12 PLATE:422
+            heads::plate_composite(Yf, D, F);
+            heads::plate_residuals(a, F, f);
             float g[5];
 #pragma unroll
             for (int i = 0; i < 5; ++i) {
                 if (q == 0) lsum[i] += vm * f[i] * f[i];
                 g[i] = 2.0f * in_loop(a.tw[i]) * f[i] * vm;
             }
-            float Fb[5][5];
-#pragma unroll
-            for (int st = 0; st < 5; ++st)
-#pragma unroll
-                for (int o = 0; o < 5; ++o) Fb[st][o] = 0.0f;
-            Fb[0][2] = g[2];
-            Fb[0][3] = g[3];
-            Fb[0][4] = g[4];
-            Fb[1][0] = -a.c1 * g[2] - a.c2 * g[3];
-            Fb[2][1] = -a.c2 * g[2] - a.c1 * g[3];
-            Fb[2][0] = -a.G * g[4];
-            Fb[1][1] = -a.G * g[4];
-            Fb[1][2] = g[0];
-            Fb[2][4] = g[0];
-            Fb[4][0] = -a.rho * g[0];
-            Fb[2][3] = g[1];
-            Fb[1][4] = g[1];
-            Fb[4][1] = -a.rho * g[1];
-#pragma unroll
-            for (int o = 0; o < 5; ++o) {
-                adj[0][o] = Fb[0][o] * D[0][o] + Fb[1][o] * D[1][o] + Fb[2][o] * D[2][o] + Fb[3][o] * D[3][o] + Fb[4][o] * D[4][o];
-                adj[1][o] = Fb[1][o] * D[0][o];
-                adj[2][o] = Fb[2][o] * D[0][o];
-                adj[3][o] = Fb[3][o] * D[0][o] + 2.0f * Fb[4][o] * D[3][o];
-                adj[4][o] = Fb[4][o] * D[0][o];
-            }
+            heads::plate_seeds(a, g, D, adjf);
         } else if constexpr (NS == 4) {
-            const float e11 = Y[1][0], e22 = Y[2][1], e12 = Y[2][0] + Y[1][1];
             float f[7];
-            f[0] = Y[1][4] + Y[2][6] - a.rho * Y[3][2];
-            f[1] = Y[2][5] + Y[1][6] - a.rho * Y[3][3];
-            f[2] = Y[3][0] - Y[0][2];
-            f[3] = Y[3][1] - Y[0][3];
-            f[4] = Y[0][4] - (a.c1 * e11 + a.c2 * e22);
-            f[5] = Y[0][5] - (a.c2 * e11 + a.c1 * e22);
-            f[6] = Y[0][6] - a.G * e12;
+            heads::wave_residuals(a, Yf, f);
             float g[7];
 #pragma unroll
             for (int i = 0; i < 7; ++i) {
                 if (q == 0) lsum[i] += vm * f[i] * f[i];
                 g[i] = 2.0f * in_loop(a.tw[i]) * f[i] * vm;
             }
-            adj[0][2] = -g[2];
-            adj[0][3] = -g[3];
-            adj[0][4] = g[4];
-            adj[0][5] = g[5];
-            adj[0][6] = g[6];
-            adj[1][0] = -a.c1 * g[4] - a.c2 * g[5];
-            adj[1][1] = -a.G * g[6];
-            adj[1][4] = g[0];
-            adj[1][6] = g[1];
-            adj[2][0] = -a.G * g[6];
-            adj[2][1] = -a.c2 * g[4] - a.c1 * g[5];
-            adj[2][5] = g[1];
-            adj[2][6] = g[0];
-            adj[3][0] = g[2];
-            adj[3][1] = g[3];
-            adj[3][2] = -a.rho * g[0];
-            adj[3][3] = -a.rho * g[1];
+            heads::wave_seeds(a, g, adjf);
         } else if (a.set_head[set] == 1) {
             // net_t PLATE:452-461 on the composite values F = P + D N (value stream only); the set's aux rows: D0[0..4], P0[5..9], nx[10], ny[11]
+            // (heads::plate_traction_residual / _seeds written out: through the calls the one-stream fused kernels' device code moves)
             const float* aux = a.set_aux[set];
             const long nn = a.set_n[set];
             float Fv[5], D0[5];
@@ -2919,6 +2813,7 @@ struct Fused {
         } else if (a.set_head[set] == 2) {
             // net_surf_var INF:267-276 on the wave net's own stresses (outputs u, v, ut, vt, s11, s22, s12), less the prescribed traction
             // (chain_kernel's HEAD_TRACTION_WAVE); the set's aux rows: nx[0], ny[1], tx[2], ty[3], normals used as given
+            // (heads::wave_traction / _seeds written out, as above)
             const float* aux = a.set_aux[set];
             const long nn = a.set_n[set];
             const float nx = aux[pidx], ny = aux[nn + pidx];
