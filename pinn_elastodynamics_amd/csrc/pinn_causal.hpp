@@ -60,8 +60,8 @@ __global__ __launch_bounds__(THREADS) void bin_partial_kernel(const BinArgs a) {
     __shared__ double qsum[4][MAX_BINS];
     __shared__ uint32_t qcount[4][MAX_BINS];
     const int b = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const uint64_t l = (uint64_t)blockIdx.x * a.chunk, h = l + a.chunk;
-    const uint32_t lo = l < a.n ? (uint32_t)l : a.n, hi = h < a.n ? (uint32_t)h : a.n;
+    uint32_t lo, hi;
+    reduce::range_of(a.chunk, a.n, lo, hi);
     double sum = 0.0;
     uint32_t count = 0;
     for (uint32_t base = lo; base < hi; base += TILE) {                        // (workgroup-uniform trip count)
@@ -98,24 +98,21 @@ __global__ __launch_bounds__(THREADS) void bin_partial_kernel(const BinArgs a) {
     }
 }
 
-// one workgroup per output k (2 * n_bins of them): thread t adds the records t, t + 256, ... of that output in that order, then the fixed tree of
-// block_sum -- the final pass of pinn_field_error_sums, spread over the outputs so that no thread walks more than MAX_BLOCKS / 256 records
+// one workgroup per output k (2 * n_bins of them): reduce::records_sum -- the final pass of pinn_field_error_sums, spread over the outputs so that
+// no thread walks more than MAX_BLOCKS / 256 records
 template <int UNUSED = 0>
 __global__ __launch_bounds__(THREADS) void bin_final_kernel(const BinArgs a) {
     __shared__ double wsum[4];
     const int k = blockIdx.x, outs = 2 * a.n_bins;
-    double s = 0.0;
-    for (int blk = threadIdx.x; blk < a.nblocks; blk += THREADS) s += a.partials[(size_t)blk * outs + k];
-    s = sample::block_sum(s, wsum);
+    const double s = reduce::records_sum(a.partials, a.nblocks, outs, k, wsum);
     if (threadIdx.x == 0) a.sums_out[k] = s;
 }
 
 // enqueue the two launches (arguments already checked, n > 0)
 inline int launch_bins(BinArgs a, void* ws, hipStream_t st) {
-    const uint32_t tiles = (a.n + TILE - 1) / TILE;
-    const int blocks = (int)(tiles < (uint32_t)MAX_BLOCKS ? tiles : MAX_BLOCKS);
-    const uint64_t per = ((uint64_t)a.n + blocks - 1) / blocks;
-    a.chunk = (uint32_t)((per + TILE - 1) / TILE * TILE);
+    const reduce::Split s = reduce::split_ranges(a.n, TILE, MAX_BLOCKS);
+    const int blocks = s.blocks;
+    a.chunk = (uint32_t)s.chunk;
     a.nblocks = blocks;
     a.partials = static_cast<double*>(ws);
     hipLaunchKernelGGL((bin_partial_kernel<0>), dim3(blocks), dim3(THREADS), 0, st, a);

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pinn_heads.hpp"
+#include "pinn_reduce.hpp"
 
 namespace pinn {
 
@@ -1368,140 +1369,71 @@ __global__ __launch_bounds__(64 * WgradCfg<WIDTH>::NW) void wgrad_kernel(const W
 // ------------------------------------------------------------------------------------------
 // small reductions / optimizer
 // ------------------------------------------------------------------------------------------
+// The summation schemes themselves -- the NaN poison of out-of-range weights, the gradient column sum, the loss-term sum, the TF1 Adam rule --
+// are defined once, in pinn_reduce.hpp; a kernel below says which blocks do what and what is written where.
+//
 // grad[p] = (accumulate ? grad[p] : 0) + scale * sum_c partial[c][p]
-// A block owns 64 parameters; its 4 waves each sum every 4th partial with four independent accumulators (the loop is
-// latency-bound otherwise), then the 16 sub-sums are combined in a fixed order: deterministic, no atomics.
+// A block owns 64 parameters (reduce::column_sum): deterministic, no atomics.
 template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void reduce_grad_kernel(const float* partial, int nchunks, int nparams, float scale,
                                                           float* grad, int accumulate) {
     __shared__ float sub[4][64];
-    const int pl = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const long p = (long)blockIdx.x * 64 + pl;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (p < nparams) {
-        int cidx = sl;
-        for (; cidx + 12 < nchunks; cidx += 16) {
-            s0 += partial[(long)cidx * nparams + p];
-            s1 += partial[(long)(cidx + 4) * nparams + p];
-            s2 += partial[(long)(cidx + 8) * nparams + p];
-            s3 += partial[(long)(cidx + 12) * nparams + p];
-        }
-        for (; cidx < nchunks; cidx += 4) s0 += partial[(long)cidx * nparams + p];
-    }
-    sub[sl][pl] = (s0 + s1) + (s2 + s3);
+    const long p = (long)blockIdx.x * 64 + (threadIdx.x & 63);
+    reduce::column_sum(partial, nchunks, nparams, sub);
     __syncthreads();
-    if (sl == 0 && p < nparams) {
-        const float s = (sub[0][pl] + sub[1][pl]) + (sub[2][pl] + sub[3][pl]);
-        grad[p] = (accumulate ? grad[p] : 0.0f) + scale * s;
-    }
+    if (threadIdx.x < 64 && p < nparams) grad[p] = (accumulate ? grad[p] : 0.0f) + scale * reduce::column_total(sub);
 }
 
 // Fused-path epilogue: reduce_grad_kernel's blocks plus one extra block per point set (the last nsets blocks) that do
 // reduce_loss_kernel's job, so that a call ends with one launch instead of two (the small configurations are bound by the chain
 // of short launches).  loss_part is [wave][slots][8] (set k in slot k); set k's sums go to loss_out.p[k][0..nterms).
 struct LossOuts { float* p[4]; int nt[4]; };      // nt[k] > 0: set k has that many terms instead of the call's `nterms` (a traction set: 2)
-template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void reduce_grad_loss_kernel(const float* partial, int nchunks, int nparams, float scale, float* grad,
-                                                               int accumulate, const float* loss_part, long nwaves, int nterms, int nsets,
-                                                               int slots, LossOuts loss_out, const int* wflags = nullptr, int nflags = 0) {
-    // Weights outside the fused format's range (repack_kernel's flags): the launch computed with infinities.  Its results are replaced by
-    // NaN as a whole -- gradient and sums -- so that the condition is unmistakable (include/pinn_hip.h, PINN_FLAG_TWO_KERNEL).
-    __shared__ int bad_weights;
-    if (threadIdx.x == 0) bad_weights = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nflags; i += 256)
-        if (wflags[i]) bad_weights = 1;
-    __syncthreads();
-    const float poison = bad_weights ? __builtin_nanf("") : 0.0f;
-    const int grad_blocks = (int)gridDim.x - nsets;
-    if ((int)blockIdx.x >= grad_blocks) {
-        const int k = (int)blockIdx.x - grad_blocks;
-        if (loss_out.nt[k] > 0) nterms = loss_out.nt[k];
-        const int term = threadIdx.x >> 5, sub = threadIdx.x & 31;
-        double s = 0.0;
-        if (term < nterms)
-            for (long w = sub; w < nwaves; w += 32) s += (double)loss_part[(w * slots + k) * 8 + term];
-        float v = (float)s;
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        v += __shfl_xor(v, 16);
-        if (sub == 0 && term < nterms && loss_out.p[k] != nullptr) loss_out.p[k][term] = v + poison;
-        return;
-    }
-    __shared__ float sub[4][64];
-    const int pl = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const long p = (long)blockIdx.x * 64 + pl;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (p < nparams) {
-        int cidx = sl;
-        for (; cidx + 12 < nchunks; cidx += 16) {
-            s0 += partial[(long)cidx * nparams + p];
-            s1 += partial[(long)(cidx + 4) * nparams + p];
-            s2 += partial[(long)(cidx + 8) * nparams + p];
-            s3 += partial[(long)(cidx + 12) * nparams + p];
-        }
-        for (; cidx < nchunks; cidx += 4) s0 += partial[(long)cidx * nparams + p];
-    }
-    sub[sl][pl] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (sl == 0 && p < nparams) {
-        const float s = (sub[0][pl] + sub[1][pl]) + (sub[2][pl] + sub[3][pl]);
-        grad[p] = (accumulate ? grad[p] : 0.0f) + scale * s + poison;
-    }
-}
-
-// The same epilogue for the stream-target sets of fused_sets_kernel (pinn_stream_loss_grad_multi): up to 8 sets, loss_part
-// [wave][slots][8] with set k in slot k.  A sibling, not a wider LossOuts: what the existing callers launch does not change.
+// The same for the stream-target sets of fused_sets_kernel (pinn_stream_loss_grad_multi): up to 8 sets.  A sibling, not a wider LossOuts: what
+// the existing callers launch does not change.
 struct LossOuts8 { float* p[8]; };
-template <int UNUSED = 0>
-__global__ __launch_bounds__(256) void reduce_grad_loss_sets_kernel(const float* partial, int nchunks, int nparams, float scale, float* grad,
-                                                                    int accumulate, const float* loss_part, long nwaves, int nterms, int nsets,
-                                                                    int slots, LossOuts8 loss_out, const int* wflags, int nflags) {
-    __shared__ int bad_weights;
-    if (threadIdx.x == 0) bad_weights = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nflags; i += 256)
-        if (wflags[i]) bad_weights = 1;
-    __syncthreads();
-    const float poison = bad_weights ? __builtin_nanf("") : 0.0f;
+__device__ __forceinline__ int set_terms(const LossOuts& o, int k, int nterms) { return o.nt[k] > 0 ? o.nt[k] : nterms; }
+__device__ __forceinline__ int set_terms(const LossOuts8&, int, int nterms) { return nterms; }
+
+// one part of a reduction: the per-workgroup gradient partials and per-wave loss records of one fused launch
+struct StepPart {
+    const float* partial;      // [nchunks][nparams]
+    int nchunks;
+    float scale;
+    const float* loss_part;
+    long nwaves;
+};
+
+template <class Outs>
+__device__ __forceinline__ void reduce_grad_loss_body(const StepPart& P, int nparams, float* grad, int accumulate, int nterms, int nsets, int slots,
+                                                      const Outs& loss_out, reduce::Flags wf, int* bad_weights, float (*sub)[64]) {
+    const float poison = reduce::weights_poison(wf.flags, wf.n, bad_weights);
     const int grad_blocks = (int)gridDim.x - nsets;
     if ((int)blockIdx.x >= grad_blocks) {
         const int k = (int)blockIdx.x - grad_blocks;
-        const int term = threadIdx.x >> 5, sub = threadIdx.x & 31;
-        double s = 0.0;
-        if (term < nterms)
-            for (long w = sub; w < nwaves; w += 32) s += (double)loss_part[(w * slots + k) * 8 + term];
-        float v = (float)s;
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        v += __shfl_xor(v, 16);
-        if (sub == 0 && term < nterms && loss_out.p[k] != nullptr) loss_out.p[k][term] = v + poison;
+        nterms = set_terms(loss_out, k, nterms);
+        const int term = threadIdx.x >> 5;
+        const float v = reduce::loss_term_sum(P.loss_part, P.nwaves, slots, k, 8, term, nterms);
+        if ((threadIdx.x & 31) == 0 && term < nterms && loss_out.p[k] != nullptr) loss_out.p[k][term] = v + poison;
         return;
     }
-    __shared__ float sub[4][64];
-    const int pl = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const long p = (long)blockIdx.x * 64 + pl;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (p < nparams) {
-        int cidx = sl;
-        for (; cidx + 12 < nchunks; cidx += 16) {
-            s0 += partial[(long)cidx * nparams + p];
-            s1 += partial[(long)(cidx + 4) * nparams + p];
-            s2 += partial[(long)(cidx + 8) * nparams + p];
-            s3 += partial[(long)(cidx + 12) * nparams + p];
-        }
-        for (; cidx < nchunks; cidx += 4) s0 += partial[(long)cidx * nparams + p];
-    }
-    sub[sl][pl] = (s0 + s1) + (s2 + s3);
+    const long p = (long)blockIdx.x * 64 + (threadIdx.x & 63);
+    reduce::column_sum(P.partial, P.nchunks, nparams, sub);
     __syncthreads();
-    if (sl == 0 && p < nparams) {
-        const float s = (sub[0][pl] + sub[1][pl]) + (sub[2][pl] + sub[3][pl]);
-        grad[p] = (accumulate ? grad[p] : 0.0f) + scale * s + poison;
-    }
+    if (threadIdx.x < 64 && p < nparams) grad[p] = (accumulate ? grad[p] : 0.0f) + P.scale * reduce::column_total(sub) + poison;
+}
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void reduce_grad_loss_kernel(StepPart P, int nparams, float* grad, int accumulate, int nterms, int nsets, int slots,
+                                                               LossOuts loss_out, reduce::Flags wf) {
+    __shared__ int bad_weights;
+    __shared__ float sub[4][64];
+    reduce_grad_loss_body(P, nparams, grad, accumulate, nterms, nsets, slots, loss_out, wf, &bad_weights, sub);
+}
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void reduce_grad_loss_sets_kernel(StepPart P, int nparams, float* grad, int accumulate, int nterms, int nsets,
+                                                                    int slots, LossOuts8 loss_out, reduce::Flags wf) {
+    __shared__ int bad_weights;
+    __shared__ float sub[4][64];
+    reduce_grad_loss_body(P, nparams, grad, accumulate, nterms, nsets, slots, loss_out, wf, &bad_weights, sub);
 }
 
 // Epilogue of fused_step_kernel (round 5): ONE launch reduces the per-workgroup partials of BOTH parts of the step launch -- A: the collocation
@@ -1515,77 +1447,33 @@ struct AdamEpilogue {
     float* v;
     float lr_t, beta1, beta2, eps;
 };
-struct StepPart {
-    const float* partial;      // [nchunks][nparams]
-    int nchunks;
-    float scale;
-    const float* loss_part;
-    long nwaves;
-};
 template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void reduce_step_kernel(StepPart A, StepPart B, int nparams, float* grad, int accumulate, int nterms_a, float* loss_a,
-                                                          int nterms_b, int nsets, int slots_b, LossOuts loss_b, AdamEpilogue adam, const int* wflags,
-                                                          int nflags) {
+                                                          int nterms_b, int nsets, int slots_b, LossOuts loss_b, AdamEpilogue adam, reduce::Flags wf) {
     __shared__ int bad_weights;
-    if (threadIdx.x == 0) bad_weights = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nflags; i += 256)
-        if (wflags[i]) bad_weights = 1;
-    __syncthreads();
-    const float poison = bad_weights ? __builtin_nanf("") : 0.0f;
+    const float poison = reduce::weights_poison(wf.flags, wf.n, &bad_weights);
     const int grad_blocks = (int)gridDim.x - nsets - 1;
     if ((int)blockIdx.x >= grad_blocks) {
         const int k = (int)blockIdx.x - grad_blocks - 1;          // -1: the collocation set, 0..nsets-1: the side sets
         const float* lp = k < 0 ? A.loss_part : B.loss_part;
         const long nw = k < 0 ? A.nwaves : B.nwaves;
-        const int slots = k < 0 ? 1 : slots_b, slot = k < 0 ? 0 : k, nterms = k < 0 ? nterms_a : (loss_b.nt[k] > 0 ? loss_b.nt[k] : nterms_b);
+        const int slots = k < 0 ? 1 : slots_b, slot = k < 0 ? 0 : k, nterms = k < 0 ? nterms_a : set_terms(loss_b, k, nterms_b);
         float* out = k < 0 ? loss_a : loss_b.p[k];
-        const int term = threadIdx.x >> 5, sub = threadIdx.x & 31;
-        double s = 0.0;
-        if (term < nterms)
-            for (long w = sub; w < nw; w += 32) s += (double)lp[(w * slots + slot) * 8 + term];
-        float v = (float)s;
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        v += __shfl_xor(v, 16);
-        if (sub == 0 && term < nterms && out != nullptr) out[term] = v + poison;
+        const int term = threadIdx.x >> 5;
+        const float v = reduce::loss_term_sum(lp, nw, slots, slot, 8, term, nterms);
+        if ((threadIdx.x & 31) == 0 && term < nterms && out != nullptr) out[term] = v + poison;
         return;
     }
     __shared__ float sub[2][4][64];
-    const int pl = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const long p = (long)blockIdx.x * 64 + pl;
-#pragma unroll
-    for (int part = 0; part < 2; ++part) {
-        const StepPart& P = part ? B : A;
-        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-        if (p < nparams) {
-            int cidx = sl;
-            for (; cidx + 12 < P.nchunks; cidx += 16) {
-                s0 += P.partial[(long)cidx * nparams + p];
-                s1 += P.partial[(long)(cidx + 4) * nparams + p];
-                s2 += P.partial[(long)(cidx + 8) * nparams + p];
-                s3 += P.partial[(long)(cidx + 12) * nparams + p];
-            }
-            for (; cidx < P.nchunks; cidx += 4) s0 += P.partial[(long)cidx * nparams + p];
-        }
-        sub[part][sl][pl] = (s0 + s1) + (s2 + s3);
-    }
+    const long p = (long)blockIdx.x * 64 + (threadIdx.x & 63);
+    reduce::column_sum(A.partial, A.nchunks, nparams, sub[0]);
+    reduce::column_sum(B.partial, B.nchunks, nparams, sub[1]);
     __syncthreads();
-    if (sl == 0 && p < nparams) {
-        const float sa = (sub[0][0][pl] + sub[0][1][pl]) + (sub[0][2][pl] + sub[0][3][pl]);
-        const float sb = (sub[1][0][pl] + sub[1][1][pl]) + (sub[1][2][pl] + sub[1][3][pl]);
-        float g = (accumulate ? grad[p] : 0.0f) + A.scale * sa + poison;      // what the collocation call's reduction wrote ...
-        g = g + B.scale * sb + poison;                                         // ... and the side-set call's added
+    if (threadIdx.x < 64 && p < nparams) {
+        float g = (accumulate ? grad[p] : 0.0f) + A.scale * reduce::column_total(sub[0]) + poison;      // what the collocation call's reduction wrote ...
+        g = g + B.scale * reduce::column_total(sub[1]) + poison;                                        // ... and the side-set call's added
         grad[p] = g;
-        if (adam.theta != nullptr) {
-            const float mi = adam.beta1 * adam.m[p] + (1.0f - adam.beta1) * g;
-            const float vi = adam.beta2 * adam.v[p] + (1.0f - adam.beta2) * g * g;
-            adam.m[p] = mi;
-            adam.v[p] = vi;
-            adam.theta[p] -= adam.lr_t * mi / (__builtin_amdgcn_sqrtf(vi) + adam.eps);
-        }
+        if (adam.theta != nullptr) reduce::adam_tf1(adam.theta, adam.m, adam.v, p, g, adam.lr_t, adam.beta1, adam.beta2, adam.eps);
     }
 }
 
@@ -1593,43 +1481,23 @@ __global__ __launch_bounds__(256) void reduce_step_kernel(StepPart A, StepPart B
 // slots per wave: 8, or LOSS_SLOTS_3D for the 3-D heads; nterms <= slots)
 template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void reduce_loss_kernel(const float* loss_part, long nwaves, int nterms, float* loss_terms,
-                                                          int accumulate, int slots, const int* wflags = nullptr, int nflags = 0) {
+                                                          int accumulate, int slots, reduce::Flags wf = reduce::Flags{nullptr, 0}) {
     // (fused 3-D path: the same NaN poisoning as reduce_grad_loss_kernel when a weight left the fused format)
     __shared__ int bad_weights;
-    if (threadIdx.x == 0) bad_weights = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < nflags; i += 256)
-        if (wflags[i]) bad_weights = 1;
-    __syncthreads();
-    const float poison = bad_weights ? __builtin_nanf("") : 0.0f;
-    const int sub = threadIdx.x & 31;
+    const float poison = reduce::weights_poison(wf.flags, wf.n, &bad_weights);
     for (int term = threadIdx.x >> 5; term < slots; term += 8) {
-        double s = 0.0;
-        if (term < nterms)
-            for (long w = sub; w < nwaves; w += 32) s += (double)loss_part[w * slots + term];
-        float v = (float)s;
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        v += __shfl_xor(v, 16);
-        if (sub == 0 && term < nterms) loss_terms[term] = (accumulate ? loss_terms[term] : 0.0f) + v + poison;
+        const float v = reduce::loss_term_sum(loss_part, nwaves, 1, 0, slots, term, nterms);
+        if ((threadIdx.x & 31) == 0 && term < nterms) loss_terms[term] = (accumulate ? loss_terms[term] : 0.0f) + v + poison;
     }
 }
 
-// tf.train.AdamOptimizer (TF1 rule; INF:131-133): epsilon added to the UNCORRECTED sqrt(v); the bias
-// correction lives in lr_t = lr * sqrt(1-beta2^t)/(1-beta1^t), computed by the caller in double.
+// pinn_adam_step: reduce::adam_tf1 on every parameter
 template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void adam_tf1_kernel(float* theta, float* m, float* v, const float* g, long n, float lr_t,
                                                        float beta1, float beta2, float eps) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i];
-    const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    theta[i] -= lr_t * mi / (__builtin_amdgcn_sqrtf(vi) + eps);
+    reduce::adam_tf1(theta, m, v, i, g[i], lr_t, beta1, beta2, eps);
 }
 
 }  // namespace pinn

@@ -464,6 +464,12 @@ struct Host {
         const long blocks = (items + 255) / 256;
         return (int)(blocks < MAX_REPACK_BLOCKS ? blocks : MAX_REPACK_BLOCKS);      // (the kernel strides: any grid covers all items)
     }
+    // what the fused path's reductions take: grid = 64 parameters per workgroup + one workgroup per loss set; repack_kernel's range flags (the
+    // formats with a range only: SPLIT == 3)
+    static dim3 epilogue_grid(const NetDesc& net, int nsets) { return dim3((net.nparams + 63) / 64 + nsets); }
+    static reduce::Flags weight_flags(const Call& c, const Plan& p) {
+        return reduce::Flags{reinterpret_cast<const int*>(static_cast<char*>(c.ws) + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0};
+    }
     static int repack(const Call& c, const Plan& p) {
         if (c.weights_packed) return 0;      // PINN_FLAG_WEIGHTS_PACKED: the previous call on this workspace left them in place
         char* b = static_cast<char*>(c.ws);
@@ -572,7 +578,7 @@ struct Host {
             toc(1);
             tic();
             hipLaunchKernelGGL((reduce_loss_kernel<0>), dim3(1), dim3(256), 0, c.stream, (const float*)a.loss_part, (long)blocks * 4, nterms,
-                               c.loss_out, pass > 0 ? 1 : 0, head_is_3d(HEAD) ? LOSS_SLOTS_3D : 8, (const int*)nullptr, 0);
+                               c.loss_out, pass > 0 ? 1 : 0, head_is_3d(HEAD) ? LOSS_SLOTS_3D : 8, reduce::Flags{nullptr, 0});
             if ((rc = (int)hipGetLastError())) return rc;
             toc(3);
             w.ntiles = nt;
@@ -583,7 +589,7 @@ struct Host {
             toc(2);
         }
         tic();
-        hipLaunchKernelGGL((reduce_grad_kernel<0>), dim3((c.net.nparams + 63) / 64), dim3(256), 0, c.stream, (const float*)w.partial,
+        hipLaunchKernelGGL((reduce_grad_kernel<0>), epilogue_grid(c.net, 0), dim3(256), 0, c.stream, (const float*)w.partial,
                            (int)NCHUNK, c.net.nparams, twmax, c.grad_out, c.accumulate);
         rc = (int)hipGetLastError();
         toc(3);
@@ -717,7 +723,6 @@ struct Host {
         constexpr int NS = K::NS, DIN = K::DIN;
         int rc = repack(c, p);
         if (rc) return rc;
-        char* b = static_cast<char*>(c.ws);
         FusedSetup su;
         fused_setup<K>(c, p, grid, nsteps, 0, 0, 0, su);
         const FusedArgs& a = su.a;
@@ -739,18 +744,17 @@ struct Host {
         }
         // loss partials are [wave][set][8] with set = FUSED_MAX_SETS slots for NS = 1 and one slot for NS = 4
         constexpr int SLOTS = NS == 1 ? FUSED_MAX_SETS : 1;
+        const StepPart P = {(const float*)a.partial, grid, twmax, (const float*)a.loss_part, (long)grid * F::TILES};
         if constexpr (DIN == 4) {
             // 12 terms in LOSS_SLOTS_3D slots per tile: the gradient blocks of the fused reduction, then the loss reduction of the two-kernel path
-            hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), dim3((c.net.nparams + 63) / 64), dim3(256), 0, c.stream, (const float*)a.partial,
-                               grid, c.net.nparams, twmax, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, 0, 0, SLOTS, lo,
-                               (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);
-            hipLaunchKernelGGL((reduce_loss_kernel<0>), dim3(1), dim3(256), 0, c.stream, (const float*)a.loss_part, (long)grid * F::TILES, nterms,
-                               c.loss_out, 0, LOSS_SLOTS_3D * SLOTS, (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);      // (NS = 1: set 0's slots of [tile][FUSED_MAX_SETS][16])
+            hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), epilogue_grid(c.net, 0), dim3(256), 0, c.stream, P, c.net.nparams, c.grad_out, c.accumulate, 0, 0,
+                               SLOTS, lo, weight_flags(c, p));
+            hipLaunchKernelGGL((reduce_loss_kernel<0>), dim3(1), dim3(256), 0, c.stream, P.loss_part, P.nwaves, nterms, c.loss_out, 0,
+                               LOSS_SLOTS_3D * SLOTS, weight_flags(c, p));      // (NS = 1: set 0's slots of [tile][FUSED_MAX_SETS][16])
             return (int)hipGetLastError();
         }
-        hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), dim3((c.net.nparams + 63) / 64 + nsets), dim3(256), 0, c.stream, (const float*)a.partial,
-                           grid, c.net.nparams, twmax, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, nterms, nsets,
-                           SLOTS, lo, (const int*)(b + p.wflags), SPLIT == 3 ? repack_blocks(c.net) : 0);
+        hipLaunchKernelGGL((reduce_grad_loss_kernel<0>), epilogue_grid(c.net, nsets), dim3(256), 0, c.stream, P, c.net.nparams, c.grad_out, c.accumulate,
+                           nterms, nsets, SLOTS, lo, weight_flags(c, p));
         return (int)hipGetLastError();
     }
 
@@ -763,7 +767,6 @@ struct Host {
                            int nterms_a, int nterms_b) {
         int rc = repack(c, p);
         if (rc) return rc;
-        char* b = static_cast<char*>(c.ws);
         FusedSetup s4, s1;
         fused_setup<K4>(c, p, grid4, nsteps4, 0, 0, 0, s4);
         fused_setup<K1>(d, p, grid1, nsteps1, 1, off1, grid4, s1);
@@ -773,9 +776,8 @@ struct Host {
         if ((rc = (int)hipGetLastError())) return rc;
         StepPart A = {(const float*)s4.a.partial, grid4, s4.twmax, (const float*)s4.a.loss_part, (long)grid4 * K4::F::TILES};
         StepPart B = {(const float*)s1.a.partial, grid1, s1.twmax, (const float*)s1.a.loss_part, (long)grid1 * K1::F::TILES};
-        hipLaunchKernelGGL((reduce_step_kernel<0>), dim3((c.net.nparams + 63) / 64 + s1.nsets + 1), dim3(256), 0, c.stream, A, B, c.net.nparams, c.grad_out,
-                           c.accumulate, nterms_a, c.loss_out, nterms_b, s1.nsets, (int)FUSED_MAX_SETS, s1.lo, adam, (const int*)(b + p.wflags),
-                           SPLIT == 3 ? repack_blocks(c.net) : 0);
+        hipLaunchKernelGGL((reduce_step_kernel<0>), epilogue_grid(c.net, s1.nsets + 1), dim3(256), 0, c.stream, A, B, c.net.nparams, c.grad_out,
+                           c.accumulate, nterms_a, c.loss_out, nterms_b, s1.nsets, (int)FUSED_MAX_SETS, s1.lo, adam, weight_flags(c, p));
         return (int)hipGetLastError();
     }
     // fused_step_kernel: the narrow layouts, and (round 6) every LDS-operand layout that has both of its parts -- the reference's own nets pay
@@ -975,9 +977,9 @@ struct Host {
             hipLaunchKernelGGL((fused_sets_kernel<Op, SPLIT, WIDTH, decltype(key)::NL>), dim3((int)grid), dim3(512), 0, c.stream, a, T);
             if (c.ring) c.ring->end(ring_slot, c.stream);
             if ((rc = (int)hipGetLastError())) { *out = rc; return 1; }
-            hipLaunchKernelGGL((reduce_grad_loss_sets_kernel<0>), dim3((c.net.nparams + 63) / 64 + c.n_ssets), dim3(256), 0, c.stream, (const float*)a.partial,
-                               (int)grid, c.net.nparams, scale, c.grad_out, c.accumulate, (const float*)a.loss_part, (long)grid * F::TILES, c.net.nout, c.n_ssets,
-                               (int)FUSED_MAX_STREAM_SETS, lo, (const int*)(static_cast<char*>(c.ws) + p.wflags), repack_blocks(c.net));
+            const StepPart P = {(const float*)a.partial, (int)grid, scale, (const float*)a.loss_part, (long)grid * F::TILES};
+            hipLaunchKernelGGL((reduce_grad_loss_sets_kernel<0>), epilogue_grid(c.net, c.n_ssets), dim3(256), 0, c.stream, P, c.net.nparams, c.grad_out,
+                               c.accumulate, c.net.nout, c.n_ssets, (int)FUSED_MAX_STREAM_SETS, lo, weight_flags(c, p));
             *out = (int)hipGetLastError();
             ++g_path_counts[FUSED_PATH];
             return 1;

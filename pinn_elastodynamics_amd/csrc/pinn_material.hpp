@@ -29,7 +29,8 @@ inline size_t ws_bytes() { return (size_t)MAX_RECORDS * MATERIAL_SUMS_MAX * size
 template <int NSUMS>
 __global__ __launch_bounds__(THREADS) void final_kernel(const double* partials, int nrecords, double* sums_out, int accumulate) {
     __shared__ double wsum[4];
-    // (the sums of a record side by side: one walk over the records instead of NSUMS -- the walk's latency is most of this launch)
+    // (the sums of a record side by side: one walk over the records instead of NSUMS -- the walk's latency is most of this launch; which is why
+    // this is not NSUMS calls of reduce::records_sum (pinn_reduce.hpp), whose order per sum it keeps)
     double s[NSUMS];
 #pragma unroll
     for (int k = 0; k < NSUMS; ++k) s[k] = 0.0;
@@ -48,8 +49,8 @@ __global__ __launch_bounds__(THREADS) void final_kernel(const double* partials, 
 template <int NSUMS>
 __global__ __launch_bounds__(THREADS) void fp32_partial_kernel(const float* terms, long m, long chunk, double* partials) {
     __shared__ double wsum[4];
-    const long l = (long)blockIdx.x * chunk, h = l + chunk;
-    const long lo = l < m ? l : m, hi = h < m ? h : m;
+    long lo, hi;
+    reduce::range_of((uint64_t)chunk, m, lo, hi);
     for (int k = 0; k < NSUMS; ++k) {
         const float* row = terms + (size_t)k * m;
         double s = 0.0;
@@ -69,12 +70,9 @@ inline int launch_final(const double* partials, int nrecords, double* sums_out, 
 // one PINN_PREC_FP32 pass of m points: its terms -> records -> added into sums_out (pass > 0) or written (pass 0)
 template <int NSUMS>
 inline int launch_fp32_pass(const float* terms, long m, double* partials, double* sums_out, int pass, hipStream_t st) {
-    long blocks = (m + THREADS - 1) / THREADS;
-    if (blocks > FP32_BLOCKS) blocks = FP32_BLOCKS;
-    const long per = (m + blocks - 1) / blocks;
-    const long chunk = (per + THREADS - 1) / THREADS * THREADS;
-    hipLaunchKernelGGL((fp32_partial_kernel<NSUMS>), dim3((unsigned)blocks), dim3(THREADS), 0, st, terms, m, chunk, partials);
-    return launch_final<NSUMS>(partials, (int)blocks, sums_out, pass > 0 ? 1 : 0, st);
+    const reduce::Split s = reduce::split_ranges((uint64_t)m, THREADS, FP32_BLOCKS);
+    hipLaunchKernelGGL((fp32_partial_kernel<NSUMS>), dim3(s.blocks), dim3(THREADS), 0, st, terms, m, (long)s.chunk, partials);
+    return launch_final<NSUMS>(partials, s.blocks, sums_out, pass > 0 ? 1 : 0, st);
 }
 
 }  // namespace material

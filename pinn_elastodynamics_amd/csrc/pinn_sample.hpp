@@ -14,8 +14,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "pinn_reduce.hpp"
+
 namespace pinn {
 namespace sample {
+
+using reduce::block_sum;                               // (pinn_reduce.hpp: the fixed-order sum over the workgroup)
 
 constexpr int THREADS = 256;
 constexpr int MAX_BLOCKS = 1024;                       // workgroups of the key launches; index ranges of the partial sums
@@ -26,6 +30,8 @@ struct Partial {                                       // one per workgroup of t
     uint64_t count;                                    // of those points
 };
 constexpr size_t WS_BYTES = (size_t)MAX_BLOCKS * sizeof(Partial);
+static_assert(sizeof(Partial) == 16 && offsetof(Partial, count) == 8, "sample_kernel walks the records as two interleaved 8-byte columns");
+static_assert(THREADS == reduce::THREADS, "block_sum, records_sum: one workgroup size");
 
 struct Words { uint32_t w[4]; };
 
@@ -151,18 +157,6 @@ __device__ __forceinline__ float q_of(const KeyArgs& a, float s) {
     return a.pow_kind == POW_ONE ? s : (a.pow_kind == POW_SQRT ? sqrtf(s) : powf(s, a.power));
 }
 
-// sum over the 256 threads of the workgroup in a fixed order (all of them call it, all get the total); `wsum` is 4 words of LDS
-template <class T>
-__device__ __forceinline__ T block_sum(T v, T* wsum) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
-    __syncthreads();           // (wsum may still be read from the previous use)
-    if (lane == 0) wsum[wave] = v;
-    __syncthreads();
-    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-
 template <int UNUSED = 0>
 __global__ __launch_bounds__(THREADS) void mask_kernel(const KeyArgs a) {
     const uint32_t stride = gridDim.x * THREADS;
@@ -170,19 +164,12 @@ __global__ __launch_bounds__(THREADS) void mask_kernel(const KeyArgs a) {
         a.key_out[i] = in_a_ball(a, i) ? -__builtin_inff() : a.score[i];
 }
 
-// the workgroup's range [lo, hi) of the mean / key launches
-__device__ __forceinline__ void range_of(const KeyArgs& a, uint32_t& lo, uint32_t& hi) {
-    const uint64_t l = (uint64_t)blockIdx.x * a.chunk, h = l + a.chunk;
-    lo = l < a.n ? (uint32_t)l : a.n;
-    hi = h < a.n ? (uint32_t)h : a.n;
-}
-
 template <int UNUSED = 0>
 __global__ __launch_bounds__(THREADS) void mean_kernel(const KeyArgs a) {
     __shared__ double dsum[4];
     __shared__ uint32_t csum[4];
     uint32_t lo, hi;
-    range_of(a, lo, hi);
+    reduce::range_of(a.chunk, a.n, lo, hi);
     double sum = 0.0;
     uint32_t count = 0;
     for (uint32_t i = lo + threadIdx.x; i < hi; i += THREADS) {
@@ -204,18 +191,12 @@ template <int UNUSED = 0>
 __global__ __launch_bounds__(THREADS) void sample_kernel(const KeyArgs a) {
     __shared__ double dsum[4];
     __shared__ uint64_t csum[4];
-    // the mean, re-derived by every workgroup: thread j adds the partials j, j + 256, ... in that order, then the fixed tree of block_sum
-    double sum = 0.0;
-    uint64_t count = 0;
-    for (uint32_t b = threadIdx.x; b < gridDim.x; b += THREADS) {
-        sum += a.partials[b].sum;
-        count += a.partials[b].count;
-    }
-    sum = block_sum(sum, dsum);
-    count = block_sum(count, csum);
+    // the mean, re-derived by every workgroup from the records (sum, count) of the mean launch: reduce::records_sum
+    const double sum = reduce::records_sum(&a.partials[0].sum, (int)gridDim.x, 2, 0, dsum);
+    const uint64_t count = reduce::records_sum(&a.partials[0].count, (int)gridDim.x, 2, 0, csum);
     const float m = count ? (float)(sum / (double)count) : 0.f;
     uint32_t lo, hi;
-    range_of(a, lo, hi);
+    reduce::range_of(a.chunk, a.n, lo, hi);
     for (uint32_t i = lo + threadIdx.x; i < hi; i += THREADS) {
         const float s = a.score[i];
         float key = -__builtin_inff();
@@ -231,16 +212,11 @@ __global__ __launch_bounds__(THREADS) void sample_kernel(const KeyArgs a) {
     }
 }
 
-inline int blocks_for(uint32_t n) {
-    const uint32_t b = (n + THREADS - 1) / THREADS;
-    return (int)(b < (uint32_t)MAX_BLOCKS ? (b ? b : 1) : MAX_BLOCKS);
-}
-
 // enqueue the key launches (arguments already checked; `a` filled but for the geometry and the workspace)
 inline int launch_keys(KeyArgs a, bool sampling, void* ws, hipStream_t st) {
-    const int blocks = blocks_for(a.n);
-    const uint64_t per = ((uint64_t)a.n + blocks - 1) / blocks;
-    a.chunk = (uint32_t)((per + THREADS - 1) / THREADS * THREADS);
+    const reduce::Split s = reduce::split_ranges(a.n, THREADS, MAX_BLOCKS);
+    const int blocks = s.blocks;
+    a.chunk = (uint32_t)s.chunk;
     a.partials = static_cast<Partial*>(ws);
     if (!sampling) {
         hipLaunchKernelGGL((mask_kernel<0>), dim3(blocks), dim3(THREADS), 0, st, a);

@@ -17,6 +17,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "pinn_reduce.hpp"
+
 namespace pinn {
 namespace select {
 
@@ -107,11 +109,10 @@ __global__ __launch_bounds__(THREADS) void count_kernel(const Args a) {
     const uint32_t thr = picked_prefix(a.hist, 4, a.k, need);
     if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t lo = (uint64_t)blockIdx.x * a.chunk;
-    const uint64_t hi64 = lo + a.chunk;
-    const uint32_t hi = hi64 < a.n ? (uint32_t)hi64 : a.n;
+    uint32_t lo, hi;
+    reduce::range_of(a.chunk, a.n, lo, hi);
     uint32_t above = 0, equal = 0;
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += THREADS) {
+    for (uint64_t i = (uint64_t)lo + threadIdx.x; i < hi; i += THREADS) {
         const uint32_t key = key_of(a.score[i], a.flip);
         above += key > thr;
         equal += key == thr;
@@ -140,9 +141,8 @@ __global__ __launch_bounds__(THREADS) void write_kernel(const Args a) {
     if (fe) atomicAdd(&front[1], fe);
     __syncthreads();
     uint32_t above0 = front[0], equal0 = front[1];
-    const uint64_t lo = (uint64_t)blockIdx.x * a.chunk;
-    const uint64_t hi64 = lo + a.chunk;
-    const uint32_t hi = hi64 < a.n ? (uint32_t)hi64 : a.n;
+    uint32_t lo, hi;
+    reduce::range_of(a.chunk, a.n, lo, hi);
     // tiles of 256 consecutive indices, in order; the flags travel through one scan: above in the low half-word, equal in the high one
     for (uint64_t base = lo; base < hi; base += THREADS) {
         const uint64_t i = base + threadIdx.x;
@@ -168,11 +168,6 @@ __global__ __launch_bounds__(THREADS) void write_kernel(const Args a) {
     }
 }
 
-inline int blocks_for(uint32_t n) {
-    const uint32_t b = (n + THREADS - 1) / THREADS;
-    return (int)(b < (uint32_t)MAX_BLOCKS ? (b ? b : 1) : MAX_BLOCKS);
-}
-
 // enqueue the selection (arguments already checked: 1 <= k <= n < 2^31, ws 256-byte aligned and >= WS_BYTES)
 inline int launch(const float* score, uint32_t n, uint32_t k, bool largest, int32_t* idx_out, void* ws, hipStream_t st) {
     Args a;
@@ -183,9 +178,9 @@ inline int launch(const float* score, uint32_t n, uint32_t k, bool largest, int3
     a.hist = static_cast<uint32_t*>(ws);
     a.counts = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + HIST_BYTES);
     a.idx_out = idx_out;
-    const int blocks = blocks_for(n);
-    const uint64_t per = ((uint64_t)n + blocks - 1) / blocks;
-    a.chunk = (uint32_t)((per + THREADS - 1) / THREADS * THREADS);
+    const reduce::Split s = reduce::split_ranges(n, THREADS, MAX_BLOCKS);
+    const int blocks = s.blocks;
+    a.chunk = (uint32_t)s.chunk;
     int rc = (int)hipMemsetAsync(a.hist, 0, HIST_BYTES, st);
     if (rc) return rc;
     hipLaunchKernelGGL((hist_kernel<0>), dim3(blocks), dim3(THREADS), 0, st, a);

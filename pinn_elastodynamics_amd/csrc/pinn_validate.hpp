@@ -35,8 +35,8 @@ inline size_t ws_bytes(int n_rows) { return (size_t)MAX_BLOCKS * 2 * n_rows * si
 template <int UNUSED = 0>
 __global__ __launch_bounds__(THREADS) void partial_kernel(const ErrArgs a) {
     __shared__ double wsum[4];
-    const uint64_t l = (uint64_t)blockIdx.x * a.chunk, h = l + a.chunk;
-    const uint32_t lo = l < a.n ? (uint32_t)l : a.n, hi = h < a.n ? (uint32_t)h : a.n;
+    uint32_t lo, hi;
+    reduce::range_of(a.chunk, a.n, lo, hi);
     for (int j = 0; j < a.n_rows; ++j) {
         const float* p = a.pred + (size_t)a.rows[j] * a.n;
         const float* r = a.ref + (size_t)j * a.n;
@@ -55,23 +55,21 @@ __global__ __launch_bounds__(THREADS) void partial_kernel(const ErrArgs a) {
     }
 }
 
-// one workgroup: thread t adds the partials t, t + 256, ... of a sum in that order, then the fixed tree of block_sum
+// one workgroup: reduce::records_sum for each sum in turn
 template <int UNUSED = 0>
 __global__ __launch_bounds__(THREADS) void final_kernel(const ErrArgs a) {
     __shared__ double wsum[4];
     for (int k = 0; k < 2 * a.n_rows; ++k) {
-        double s = 0.0;
-        for (int b = threadIdx.x; b < a.nblocks; b += THREADS) s += a.partials[(size_t)b * 2 * a.n_rows + k];
-        s = sample::block_sum(s, wsum);
+        const double s = reduce::records_sum(a.partials, a.nblocks, (size_t)2 * a.n_rows, k, wsum);
         if (threadIdx.x == 0) a.sums_out[k] = s;
     }
 }
 
 // enqueue the two launches (arguments already checked, n > 0)
 inline int launch(ErrArgs a, void* ws, hipStream_t st) {
-    const int blocks = sample::blocks_for(a.n) < MAX_BLOCKS ? sample::blocks_for(a.n) : MAX_BLOCKS;
-    const uint64_t per = ((uint64_t)a.n + blocks - 1) / blocks;
-    a.chunk = (uint32_t)((per + THREADS - 1) / THREADS * THREADS);
+    const reduce::Split s = reduce::split_ranges(a.n, THREADS, MAX_BLOCKS);
+    const int blocks = s.blocks;
+    a.chunk = (uint32_t)s.chunk;
     a.nblocks = blocks;
     a.partials = static_cast<double*>(ws);
     hipLaunchKernelGGL((partial_kernel<0>), dim3(blocks), dim3(THREADS), 0, st, a);
